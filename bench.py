@@ -8,8 +8,17 @@ forward + Z, residual loss, second-order backward, [RCCL all-reduce], Adam.
 All inputs resident in HBM.  value = total SDE path-steps/s over all ranks
 (weak scaling: 1024 paths per GPU; --strong: 1024 paths in total, split).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(value, ms_per_step, configuration).  --dump-outputs DIR also writes what the
+last timed step handed back (loss, gradient, updated parameters) as
+DIR/<name>.npy.  --full adds everything else to the line, each from runs of its
+own after the timed window: the all-reduce latency, the per-kernel HIP-event
+pass and its rooflines, u(0, X0) of the bench model, the torch-CPU baseline
+and the 100-step parity trajectory (--no-cpu-baseline / --no-parity leave the
+last two out of a --full run).
 
 --workload oned|basket|hjb|heston runs BASELINE configs 1 and 3-5 on this
 process's GPUs (separate lines for DESIGN.md; the headline is the default bsb
@@ -212,9 +221,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--strong", action="store_true", help="global batch fixed at the workload's M (split)")
     ap.add_argument("--workload", default="bsb", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, grad, params) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also measure the all-reduce, the per-kernel event pass and "
+                         "rooflines, u(0,X0), the CPU baseline and the parity trajectory")
     ap.add_argument("--cpu-iters", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the 100-step Y0 parity trajectory")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the 100-step Y0 parity trajectory")
     ap.add_argument("--paths-per-gpu", type=int, default=None,
                     help="paths per GPU (default: the workload's M); e.g. 128/256/512 = the per-rank shapes of "
                          "8/4/2-GPU strong scaling")
@@ -222,6 +237,8 @@ def main():
     ap.add_argument("--activation", default=None, help="experiments only; the headline is Sine")
     ap.add_argument("--mode", default=None, help="experiments only; the headline is NAIS-Net")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -263,7 +280,58 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e)
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
 
+    ms_per_step = 1000.0 * elapsed / args.steps
+    total_path_steps = M_global * wl["N"]
+    value = total_path_steps * args.steps / elapsed
+    Mloc = M_global // world
+    out = {
+        "metric": "SDE-path-steps/sec + |u(0,X_0) err|, 100-D BSB, 1/2/4/8 MI355X",
+        "value": value,
+        "unit": "path-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic: device Philox Brownian increments, reference (xavier) init weights, seed 0",
+        "config": {"workload": wl["desc"], "name": args.workload, "D": wl["D"], "layers": wl["layers"],
+                   "mode": args.mode or wl["mode"], "activation": args.activation or wl["act"],
+                   "paths_per_gpu": Mloc, "global_batch": M_global, "time_steps": wl["N"],
+                   "parallelism": f"dp{world}"},
+        "per_gpu_path_steps_per_s": value / world,
+        "final_loss": final_loss,
+    }
+    if args.full:
+        # every rank runs the extra passes (the all-reduce is collective); rank 0 reports
+        extra = full_measurements(pkg, model, opt, args, wl, world, rank, dev, it, barrier, ms_per_step, final_loss)
+        if rank == 0:
+            out.update(extra)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, model, loss):
+    """What a caller of the timed path holds after its last step, as
+    <path>/<name>.npy (float32, under 3 MB in all for every workload): the loss device_step
+    returned, the gradient it left in model.grad and the parameters it
+    updated.  Seeds, initial weights and step seeds are fixed, so the same
+    arguments give the same inputs from run to run."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in (("loss", loss), ("grad", model.grad), ("params", model.params)):
+        np.save(os.path.join(path, name + ".npy"), v.detach().reshape(-1).to(torch.float32).cpu().numpy())
+
+
+def full_measurements(pkg, model, opt, args, wl, world, rank, dev, it, barrier, ms_per_step, final_loss):
+    """The --full extras, measured after the timed window in runs of their
+    own; returns the keys they add to the result line (None off rank 0)."""
     # the one collective per step, alone: [grad | loss] all-reduce latency
     allreduce_us = None
     if world > 1:
@@ -292,13 +360,7 @@ def main():
     u0 = float(u0)
 
     if rank != 0:
-        if world > 1:
-            dist.destroy_process_group()
-        return
-
-    ms_per_step = 1000.0 * elapsed / args.steps
-    total_path_steps = M_global * wl["N"]
-    value = total_path_steps * args.steps / elapsed
+        return None
 
     # roofline of the dominant MFMA kernel (the main-stream network passes;
     # side-stream launches such as loss_final include queue wait in their events)
@@ -364,29 +426,11 @@ def main():
     if not args.no_parity and args.workload == "bsb":
         parity = parity_trajectory(pkg, dev)
 
-    Mloc = M_global // world
-    out = {
-        "metric": "SDE-path-steps/sec + |u(0,X_0) err|, 100-D BSB, 1/2/4/8 MI355X",
-        "value": value,
-        "unit": "path-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic: device Philox Brownian increments, reference (xavier) init weights, seed 0",
-        "config": {"workload": wl["desc"], "name": args.workload, "D": wl["D"], "layers": wl["layers"],
-                   "mode": args.mode or wl["mode"], "activation": args.activation or wl["act"],
-                   "paths_per_gpu": Mloc, "global_batch": M_global, "time_steps": wl["N"],
-                   "parallelism": f"dp{world}"},
+    return {
         "roofline": roofline,
         "roofline_other_mfma": roofline_others,
         "roofline_path_step": roofline_path,
         "allreduce_us": allreduce_us,
-        "per_gpu_path_steps_per_s": value / world,
         "step_alg_tflops": step_flops / (ms_per_step * 1e-3) / 1e12,
         "step_kernel_ms": breakdown,
         "accuracy": {"parity": parity,
@@ -398,9 +442,6 @@ def main():
                                              "exact value 77.1049 (DeepBSDE.py:345-349) needs ~2e4 iterations"}},
         "cpu_baseline": cpu,
     }
-    print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -15,12 +15,12 @@ step() {  # step <name> <seconds> <cmd...>
   echo "$name rc=$rc" | tee -a $out/steps.log
   [ $rc -eq 0 ] || { tail -20 "$out/$name.log"; exit $rc; }
 }
-step bench 400 python bench.py
+step bench 400 python bench.py --full
 for w in basket hjb heston; do
-  step wl_$w 300 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline
+  step wl_$w 300 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline
 done
 for m in 512 256 128; do
-  step m$m 300 python bench.py --paths-per-gpu $m --steps 50 --warmup 10 --no-cpu-baseline --no-parity
+  step m$m 300 python bench.py --full --paths-per-gpu $m --steps 50 --warmup 10 --no-cpu-baseline --no-parity
 done
 step stats 300 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity
 echo done
