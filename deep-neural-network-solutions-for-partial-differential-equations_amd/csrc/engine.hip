@@ -56,6 +56,7 @@
 #include "phase.hpp"
 #include "phase2.hpp"
 #include "phasecs.hpp"
+#include "xbar.hpp"
 
 // minimum rows per weight-gradient row split of the chain layouts: 448 keeps
 // HJB's 43,008 rows at the 96-split capacity (1.222-1.232 ms/step against
@@ -191,6 +192,10 @@ struct dbsde_ctx {
   unsigned char* d_used = nullptr;
   PackDesc* d_prep = nullptr;
   int n_prep = 0;
+  // fused contexts: the BtZ packs the phase kernels' images stand in for, run
+  // only where BtZ itself is read (dbsde_net_u_xvjp's input cotangent)
+  PackDesc* d_prepz = nullptr;
+  int n_prepz = 0, prepz_blocks = 1;
 
   int prep_blocks = 1;   // pack_tagged_kernel grid.x: one element per thread
   PackDesc* d_fin = nullptr;
@@ -702,7 +707,7 @@ int build_buffers(dbsde_ctx* c) {
   };
 
   // ---- prep descriptors: flat params -> packed weight buffers
-  std::vector<PackDesc> P;
+  std::vector<PackDesc> P, PZ;
   auto add_x_level = [&](int j, const Lin& w, const Lin* b2) {
     float* dst = c->BtIn + (size_t)c->col[j] * Dp;
     P.push_back(frag(mk_desc(ptag(w.w), D + 1, dst, Dp, w.out, D + 1, 0, PK_COPY), c->imgX[j], TDp, TW, 0, 0));
@@ -714,8 +719,9 @@ int build_buffers(dbsde_ctx* c) {
     } else {
       P.push_back(frag(mk_desc(ptag(w.b), 1, dst + D + 1, Dp, w.out, 1, 0, PK_COPY), c->imgX[j], TDp, TW, 0, D + 1));
     }
-    P.push_back(frag(mk_desc(ptag(w.w), D + 1, c->BtZ + c->col[j], c->Stot_x, w.out, D + 1, 1, PK_COPY), c->imgZ[j],
-                     TW, TDp, 0, 0));
+    const PackDesc z = mk_desc(ptag(w.w), D + 1, c->BtZ + c->col[j], c->Stot_x, w.out, D + 1, 1, PK_COPY);
+    P.push_back(frag(z, c->imgZ[j], TW, TDp, 0, 0));
+    if (images_only) PZ.push_back(z);
   };
   add_x_level(0, c->in, nullptr);
   if (c->has_v)
@@ -872,6 +878,12 @@ int build_buffers(dbsde_ctx* c) {
     HIPC(c, hipMemcpy(c->d_fintab, &tab, sizeof(tab), hipMemcpyHostToDevice));
   }
   if ((rc = dalloc_t(c, &c->d_prep, P.size()))) return rc;
+  c->n_prepz = (int)PZ.size();
+  if (c->n_prepz) {
+    for (const PackDesc& d : PZ) c->prepz_blocks = std::max(c->prepz_blocks, (d.rows * d.cols + 255) / 256);
+    if ((rc = dalloc_t(c, &c->d_prepz, PZ.size()))) return rc;
+    HIPC(c, hipMemcpy(c->d_prepz, PZ.data(), PZ.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
+  }
   if ((rc = dalloc_t(c, &c->d_fin, F.size()))) return rc;
   // descriptors are stored with tagged pointers; the kernel arguments carry the
   // real params/grad bases (pack_kernel_tagged below).
@@ -2160,6 +2172,7 @@ int backward_tail(dbsde_ctx* c, const float* params, int R, int Rp, int fv, floa
         return rc;
     }
   }
+  if (!grad) return DBSDE_OK;   // (dbsde_net_u_xvjp without grad: the sweeps above completed Alpha)
   // ---- parameter gradients
   if (c->tnw) {
     if (!tnw_piped && (rc = launch_tnw(c, R, Rp))) return rc;
@@ -2478,6 +2491,71 @@ int make_optargs(dbsde_ctx* c, const dbsde_optim* o, OptArgs& a) {
   }
   return DBSDE_OK;
 }
+// dbsde_net_u_vjp / dbsde_net_u_xvjp: grad (nullable) and xbar (nullable, [R, D])
+int net_u_vjp_impl(dbsde_ctx* c, const float* params, int R, const float* t, const float* X, const float* ubar,
+                   const float* zbar, float* grad, float* xbar) {
+  HIPC(c, hipSetDevice(c->device));
+  const int Rp = (R + ROW_PAD - 1) / ROW_PAD * ROW_PAD, D = c->D;
+  int rc;
+  if ((rc = ensure_rows(c, Rp, 1))) return rc;
+  hipStream_t s = c->stream;
+  if ((rc = prep_weights(c, params))) return rc;
+  bool from_pf;
+  if ((rc = flush_deferred(c))) return rc;
+  if ((rc = select_paths(c, nullptr, from_pf))) return rc;
+  const long long n = (long long)Rp * c->Dp;
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  RUN(c, "netu_input", 0.0, 0.0, netu_input_kernel<<<nb, 256, 0, s>>>(t, X, R, D, c->Dp, c->xin));
+  if (Rp > R) HIPC(c, hipMemsetAsync(c->xin + (size_t)R * c->Dp, 0, (size_t)(Rp - R) * c->Dp * 4, s));
+  // xbar = (Alpha[:, :Stot_x] . W)[:, 1..D] once Alpha is final (fused: after
+  // phase C; per-layer form: after backward_tail's reverse sweep)
+  auto input_cotangent = [&]() -> int {
+    if (c->n_prepz)   // fused contexts pack only the fragment images per step
+      RUN(c, "pack_weights_z", 0.0, 0.0,
+          pack_tagged_kernel<<<dim3(c->prepz_blocks, c->n_prepz), 256, 0, s>>>(c->d_prepz, params, nullptr));
+    XbarArgs xa{};
+    xa.Alpha = c->Alpha;
+    xa.lda = c->Stot;
+    xa.Wt = c->BtZ;
+    xa.K = c->Stot_x;
+    xa.Dp = c->Dp;
+    xa.R = R;
+    xa.D = D;
+    xa.xbar = xbar;
+    int ok = 0;
+    RUN(c, "netu_xbar", 2.0 * R * c->Stot_x * (double)D, 4.0 * (R * ((double)c->Stot_x + D) + (double)c->Stot_x * c->Dp),
+        ok = netu_xbar_launch(xa, s));
+    if (ok) return fail(c, DBSDE_EINVAL, "internal: netu_xbar geometry");
+    return DBSDE_OK;
+  };
+  const int fv = c->fv;
+  if (fv >= 0) {
+    // ubar -> rres rows, zbar -> the sdw rows phase C reads (phase A's use of
+    // sdw only feeds the residual row sums, unused here)
+    RUN(c, "vjp_cotangents", 0.0, 0.0,
+        ext_cotan_kernel<<<nb, 256, 0, s>>>(ubar, zbar, R, Rp, D, c->Dp, nullptr, c->rres, c->sdw, nullptr));
+    FusedArgs fa = fused_args(c, R, Rp, 1, false);
+    if (!fused_piece_counts_ok(c, fa)) return fail(c, DBSDE_EINVAL, "internal: fused kernel piece counts");
+    fa.cp.ext = 1;
+    fa.cp.ext_ub = c->rres;
+    const int WR = kFused[fv].rows;
+    RUN(c, "fused_fwd_inputgrad", 0.0, 0.0, kFused[fv].A<<<Rp / WR, 64 * P3_WAVES, 0, s>>>(fa));
+    RUN(c, "fused_tangent_reverse", 0.0, 0.0, kFused[fv].C<<<Rp / WR, 64 * P3_WAVES, 0, s>>>(fa));
+    if (xbar && (rc = input_cotangent())) return rc;
+    if (!grad) return DBSDE_OK;   // no weight-gradient launches, no finalize
+  } else {
+    if ((rc = flush_deferred(c, c->xin))) return rc;
+    if ((rc = forward_and_inputgrad(c, R, Rp, false))) return rc;
+    RUN(c, "vjp_cotangents", 0.0, 0.0,
+        ext_cotan_kernel<<<nb, 256, 0, s>>>(ubar, zbar, R, Rp, D, c->Dp, c->u_clamp ? c->umask : nullptr, c->ubar,
+                                            c->zbar, c->u16));
+  }
+  c->tnw_S = tnw_slices(c, Rp);
+  if ((rc = backward_tail(c, params, R, Rp, fv, grad, nullptr, 0, nullptr, nullptr, false, false))) return rc;
+  if (fv < 0 && xbar && (rc = input_cotangent())) return rc;
+  return DBSDE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2559,41 +2637,18 @@ int dbsde_net_u_vjp(dbsde_ctx* c, const float* params, int R, const float* t, co
                     const float* zbar, float* grad) {
   if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
   if (!params || !t || !X || !ubar || !zbar || !grad || R < 1) return fail(c, DBSDE_EINVAL, "bad net_u_vjp arguments");
-  HIPC(c, hipSetDevice(c->device));
-  const int Rp = (R + ROW_PAD - 1) / ROW_PAD * ROW_PAD, D = c->D;
-  int rc;
-  if ((rc = ensure_rows(c, Rp, 1))) return rc;
-  hipStream_t s = c->stream;
-  if ((rc = prep_weights(c, params))) return rc;
-  bool from_pf;
-  if ((rc = flush_deferred(c))) return rc;
-  if ((rc = select_paths(c, nullptr, from_pf))) return rc;
-  const long long n = (long long)Rp * c->Dp;
-  const unsigned nb = (unsigned)((n + 255) / 256);
-  RUN(c, "netu_input", 0.0, 0.0, netu_input_kernel<<<nb, 256, 0, s>>>(t, X, R, D, c->Dp, c->xin));
-  if (Rp > R) HIPC(c, hipMemsetAsync(c->xin + (size_t)R * c->Dp, 0, (size_t)(Rp - R) * c->Dp * 4, s));
-  const int fv = c->fv;
-  if (fv >= 0) {
-    // ubar -> rres rows, zbar -> the sdw rows phase C reads (phase A's use of
-    // sdw only feeds the residual row sums, unused here)
-    RUN(c, "vjp_cotangents", 0.0, 0.0,
-        ext_cotan_kernel<<<nb, 256, 0, s>>>(ubar, zbar, R, Rp, D, c->Dp, nullptr, c->rres, c->sdw, nullptr));
-    FusedArgs fa = fused_args(c, R, Rp, 1, false);
-    if (!fused_piece_counts_ok(c, fa)) return fail(c, DBSDE_EINVAL, "internal: fused kernel piece counts");
-    fa.cp.ext = 1;
-    fa.cp.ext_ub = c->rres;
-    const int WR = kFused[fv].rows;
-    RUN(c, "fused_fwd_inputgrad", 0.0, 0.0, kFused[fv].A<<<Rp / WR, 64 * P3_WAVES, 0, s>>>(fa));
-    RUN(c, "fused_tangent_reverse", 0.0, 0.0, kFused[fv].C<<<Rp / WR, 64 * P3_WAVES, 0, s>>>(fa));
-  } else {
-    if ((rc = flush_deferred(c, c->xin))) return rc;
-    if ((rc = forward_and_inputgrad(c, R, Rp, false))) return rc;
-    RUN(c, "vjp_cotangents", 0.0, 0.0,
-        ext_cotan_kernel<<<nb, 256, 0, s>>>(ubar, zbar, R, Rp, D, c->Dp, c->u_clamp ? c->umask : nullptr, c->ubar,
-                                            c->zbar, c->u16));
-  }
-  c->tnw_S = tnw_slices(c, Rp);
-  return backward_tail(c, params, R, Rp, fv, grad, nullptr, 0, nullptr, nullptr, false, false);
+  return net_u_vjp_impl(c, params, R, t, X, ubar, zbar, grad, nullptr);
+}
+
+// The same with the input cotangent: xbar = d/dX of the same scalar = ubar Du
+// + H zbar, the reverse cotangents alpha_j the backward already forms
+// contracted with the input-facing weights (xbar.hpp).
+int dbsde_net_u_xvjp(dbsde_ctx* c, const float* params, int R, const float* t, const float* X, const float* ubar,
+                     const float* zbar, float* grad, float* xbar) {
+  if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
+  if (!params || !t || !X || !ubar || !zbar || (!grad && !xbar) || R < 1)
+    return fail(c, DBSDE_EINVAL, "bad net_u_xvjp arguments");
+  return net_u_vjp_impl(c, params, R, t, X, ubar, zbar, grad, xbar);
 }
 
 int dbsde_optimizer_step(dbsde_ctx* c, float* params, float* grad, float* m, float* v, const dbsde_optim* o) {

@@ -63,8 +63,11 @@ def _world():
 
 class _NetU(torch.autograd.Function):
     """FBSNN.net_u as a differentiable op: forward dbsde_net_u, backward the
-    native VJP dbsde_net_u_vjp (parameter gradients of sum ubar u + zbar . Du),
-    split into the model parameters."""
+    native VJP dbsde_net_u_xvjp of sum ubar u + zbar . Du -- the parameter
+    gradient, split into the model parameters, and the input cotangent
+    xbar = ubar Du + H zbar for the points X, each only when asked for.  t is
+    not differentiated.  Once differentiable: a derivative of xbar (third
+    order in the network) raises."""
 
     @staticmethod
     def forward(ctx, fb, t, X, *params):
@@ -82,9 +85,14 @@ class _NetU(torch.autograd.Function):
         t, X = ctx.saved_tensors
         gu = torch.zeros(X.shape[0], device=X.device) if gu is None else gu.reshape(-1).float().contiguous()
         gdu = torch.zeros_like(X) if gdu is None else gdu.float().contiguous()
-        g = torch.empty_like(fb.params)
-        fb.solver.net_u_vjp(fb.params, t, X, gu, gdu, g)
-        return (None, None, None) + fb._param_grads(g)
+        need_x, need_p = ctx.needs_input_grad[2], any(ctx.needs_input_grad[3:])
+        if not (need_x or need_p):
+            return (None,) * len(ctx.needs_input_grad)
+        g = torch.empty_like(fb.params) if need_p else None
+        xb = torch.empty_like(X) if need_x else None
+        fb.solver.net_u_xvjp(fb.params, t, X, gu, gdu, grad=g, xbar=xb)
+        pg = fb._param_grads(g) if need_p else (None,) * (len(ctx.needs_input_grad) - 3)
+        return (None, None, xb) + pg
 
 
 class _Loss(torch.autograd.Function):
@@ -331,15 +339,21 @@ class FBSNN(ABC):
         """DeepBSDE.py:189-194: (u [R,1], Du [R,D]) at the given points.  With
         grad mode on, (u, Du) are connected to the model parameters as in the
         reference (nd_BSPDE_case.py:191-221, create_graph=True): a backward
-        through them runs the native VJP (dbsde_net_u_vjp) and accumulates
-        into each parameter's .grad.  The points are not differentiated."""
+        through them runs the native VJP (dbsde_net_u_xvjp) and accumulates
+        into each parameter's .grad.  They are differentiable in the points
+        too: when X requires grad, the same backward returns d/dX of the
+        cotangent-weighted outputs (ubar Du + H zbar), so
+        torch.autograd.functional.jacobian(lambda s: net_u(t, s)[0], S) and
+        autograd.grad(Du, X, ...) (a Hessian-vector product: gamma) work as
+        against the reference.  t is not differentiated, and a derivative of
+        that X gradient itself (third order) raises."""
         X = torch.as_tensor(X, dtype=torch.float32).to(self.device)
         if X.dim() == 1:
             X = X.unsqueeze(-1)
-        t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1).contiguous()
-        X = X.detach().reshape(-1, self.state_dim).contiguous()
+        t = torch.as_tensor(t, dtype=torch.float32).to(self.device).detach().reshape(-1).contiguous()
+        X = X.reshape(-1, self.state_dim).contiguous()
         params = [p for _, p in self.model.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        if torch.is_grad_enabled() and (X.requires_grad or any(p.requires_grad for p in params)):
             return _NetU.apply(self, t, X, *params)
         u = torch.empty((X.shape[0], 1), device=self.device)
         du = torch.empty_like(X)

@@ -242,6 +242,29 @@ class HestonFBSNN(FBSNN):
         k = self.n_assets
         return X[:, :, :k], X[:, :, k:], Y
 
+    def calculate_greeks(self, S, v, t):
+        """heston_dnnpde.py:685-699 -> numpy (Y [R, 1], delta [R, k], gamma).
+
+        S and v hold the R evaluation points ([R] at k = 1, as the reference
+        passes them, or [R, k]); t the R times.  delta = dU/dS is net_u's Du
+        over the S columns, and gamma = autograd.grad(delta, S, ones_like(delta))
+        in the reference's expression order, so gamma has S's shape.  At k = 1
+        that is d2U/dS2.  For k > 1 the all-ones cotangent sums the Hessian
+        block over assets: gamma[r, i] = sum_j d2U / dS_i dS_j at point r (the
+        row sums of the S-S Hessian block, not its diagonal).  Through the
+        u clamp: Y, delta and gamma are 0 where the network output is negative.
+        The Hessian-vector product is one native dbsde_net_u_xvjp."""
+        k = self.n_assets
+        S = torch.tensor(np.asarray(S), dtype=torch.float32, device=self.device, requires_grad=True)
+        v = torch.tensor(np.asarray(v), dtype=torch.float32, device=self.device, requires_grad=True)
+        t = torch.tensor(np.asarray(t), dtype=torch.float32, device=self.device)
+        with torch.enable_grad():
+            X = torch.cat([S.reshape(-1, k), v.reshape(-1, k)], dim=1)
+            Y, Du = self.net_u(t.reshape(-1), X)
+            delta = Du[:, :k]
+            gamma = torch.autograd.grad(delta, S, grad_outputs=torch.ones_like(delta))[0]
+        return Y.detach().cpu().numpy(), delta.detach().cpu().numpy(), gamma.detach().cpu().numpy()
+
 
 __all__ = ["CallOption", "CallOption1D", "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN"]

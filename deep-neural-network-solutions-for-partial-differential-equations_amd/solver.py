@@ -197,6 +197,26 @@ class NativeSolver:
         _lib.check(self.lib.dbsde_net_u_vjp(self.ctx, _ptr(params), R, _ptr(t), _ptr(X), _ptr(ubar), _ptr(zbar),
                                             _ptr(grad)), self.ctx)
 
+    def net_u_xvjp(self, params, t, X, ubar, zbar, grad=None, xbar=None):
+        """The same backward with the input cotangent (dbsde_net_u_xvjp):
+        grad <- d/dparams and xbar [R, D] <- d/dX of [sum ubar u + sum zbar . Du]
+        at (t, X), i.e. xbar = ubar Du + H zbar.  Each is optional (None: not
+        computed); at least one is required."""
+        if grad is None and xbar is None:
+            raise ValueError("net_u_xvjp needs grad, xbar or both")
+        R = X.numel() // self.D
+        self._check_tensor(params, "params", self.nparams)
+        for name, v, n in (("t", t, R), ("X", X, R * self.D), ("ubar", ubar, R), ("zbar", zbar, R * self.D)):
+            self._check_tensor(v, name, n)
+        if grad is not None:
+            self._check_tensor(grad, "grad", self.nparams)
+        if xbar is not None:
+            self._check_tensor(xbar, "xbar", R * self.D)
+        self._bind_stream()
+        _lib.check(self.lib.dbsde_net_u_xvjp(self.ctx, _ptr(params), R, _ptr(t), _ptr(X), _ptr(ubar), _ptr(zbar),
+                                             _ptr(grad) if grad is not None else None,
+                                             _ptr(xbar) if xbar is not None else None), self.ctx)
+
     def optimizer_step(self, params, grad, m, v, **opt):
         """clip_grad_norm_ + optimizer.step() over the flat parameters; m, v are
         the optimizer's state buffers (see include/dbsde.h DBSDE_OPT_*); opt as

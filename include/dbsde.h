@@ -243,10 +243,24 @@ int dbsde_net_u(dbsde_ctx* ctx, const float* params, int R, const float* t,
  * graph of (u, Du) delivers (nd_BSPDE_case.py:191-221, create_graph=True),
  *   grad = d/dparams [ sum_r ubar[r] u[r] + sum_{r,d} zbar[r,d] Du[r,d] ]
  * at the R points (t [R], X [R,D]); ubar [R], zbar [R,D], grad (flat,
- * param_count) are device buffers (grad overwritten).  Not the gradient with
- * respect to X. */
+ * param_count) are device buffers (grad overwritten).  The gradient with
+ * respect to X is dbsde_net_u_xvjp's. */
 int dbsde_net_u_vjp(dbsde_ctx* ctx, const float* params, int R, const float* t,
                     const float* X, const float* ubar, const float* zbar, float* grad);
+
+/* The same backward with the input cotangent (net_u differentiated in the
+ * points: the reference's jacobian(net_u, S) and its Greeks,
+ * with_corr_high_dimension_pde.py:856-877, heston_dnnpde.py:685-699):
+ *   xbar[r, :] = d/dX_r [ ubar[r] u[r] + zbar[r, :] . Du[r, :] ]
+ *              = ubar[r] Du[r, :] + H_r zbar[r, :],   H_r = the Hessian of u in X at row r
+ * (Heston: through the u clamp, so 0 on the clamped rows).  xbar [R, D] device,
+ * overwritten.  grad and xbar are each optional (NULL: not computed; with grad
+ * NULL the weight-gradient work is skipped where it is a separate launch);
+ * both NULL is DBSDE_EINVAL.  grad is filled exactly as dbsde_net_u_vjp fills
+ * it.  t is not differentiated.  The result is bitwise repeatable. */
+int dbsde_net_u_xvjp(dbsde_ctx* ctx, const float* params, int R, const float* t,
+                     const float* X, const float* ubar, const float* zbar, float* grad,
+                     float* xbar);
 
 /* optimizers (nd_BSPDE_case.py:331-350), torch.optim single-tensor formula order */
 #define DBSDE_OPT_ADAM 0
