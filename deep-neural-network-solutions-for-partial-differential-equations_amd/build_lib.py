@@ -9,12 +9,16 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-# translation units and their extra flags: the weight-gradient kernel is built
-# with VGPR-form MFMA (see csrc/tnw.hip); everything else (its split-bf16 form
-# tnwx3.hip included: accumulators in AGPRs; xbar.hip: net_u's input cotangent)
-# with the defaults
-UNITS = [("engine.hip", []), ("phase2.hip", []), ("phasecs.hip", []), ("evals.hip", []), ("tnw.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=true"]),
-         ("tnwx3.hip", []), ("xbar.hip", [])]
+# translation units and their extra flags.  The host code behind the C ABI is
+# split by concern over net.hip (context, buffers, streams), rollout.hip (path
+# kernels and the prefetch scheduler), step.hip (the step, net_u, the
+# optimizer; the phase, chain and finalize kernels) and vec.hip (L-BFGS vector
+# operations); csrc/ctx.hpp is what they share.  The weight-gradient kernel is
+# built with VGPR-form MFMA (see csrc/tnw.hip); everything else (its split-bf16
+# form tnwx3.hip included: accumulators in AGPRs; xbar.hip: net_u's input
+# cotangent) with the defaults
+UNITS = [("step.hip", []), ("net.hip", []), ("rollout.hip", []), ("vec.hip", []), ("phase2.hip", []), ("phasecs.hip", []),
+         ("evals.hip", []), ("tnw.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=true"]), ("tnwx3.hip", []), ("xbar.hip", [])]
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))] + \
     [os.path.join(ROOT, "include", "dbsde.h")]
 OUT = os.path.join(HERE, "lib", "libdbsde.so")

@@ -1180,6 +1180,237 @@ __global__ void __launch_bounds__(256) tilefin_kernel(const TileFinTable* tab, c
     if (threadIdx.x == 0) dotd->dot_part[blockIdx.x] = (dps[0] + dps[1]) + (dps[2] + dps[3]);
   }
 }
+
+// tagged-pointer fixup happens inside a thin wrapper kernel
+__device__ __forceinline__ const float* untag(const float* p, const float* params, const float* grad) {
+  uintptr_t v = (uintptr_t)p;
+  if (v & ((uintptr_t)1 << 62)) return params + ((v & (((uintptr_t)1 << 61) - 1)) >> 2);
+  if (v & ((uintptr_t)1 << 61)) return grad + ((v & (((uintptr_t)1 << 61) - 1)) >> 2);
+  return p;
+}
+__device__ __forceinline__ void pack_block(const PackDesc* descs, int di, const float* params, float* grad) {
+  PackDesc d = descs[di];
+  d.src = untag(d.src, params, grad);
+  d.src2 = untag(d.src2, params, grad);
+  d.dst = (float*)untag(d.dst, params, grad);
+  const int total = d.rows * d.cols;
+  if ((int)blockIdx.x * 256 >= total) return;
+  // the first element's source value in the round of the norm partials below
+  const int i0 = blockIdx.x * 256 + threadIdx.x;
+  const float rv0 = (d.mode == PK_NEGPROJ && i0 < total) ? d.src[(size_t)(i0 / d.cols) * d.src_ld + i0 % d.cols] : 0.f;
+  // NAIS projection: |RtR|_F from rtr_params_kernel's partials (fixed order)
+  __shared__ float nrm_s;
+  if (d.mode == PK_NEGPROJ) {
+    if (threadIdx.x < 64) {   // wave 0: lane b holds partials b, b + 64, ... ; fixed-order butterfly
+      double sq = 0.0;
+      for (int b = threadIdx.x; b < d.proj_n; b += 64) sq += d.proj[b];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+      if (threadIdx.x == 0) {
+        const double n = sqrt(sq);
+        nrm_s = (float)n;
+        if (blockIdx.x == 0 && d.proj_norm) *d.proj_norm = n;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int r = i / d.cols, cc = i - r * d.cols;
+    float v;
+    if (d.mode == PK_COPY) {
+      v = d.scale * d.src[(size_t)r * d.src_ld + cc];
+    } else if (d.mode == PK_ADD2) {
+      v = d.src[(size_t)r * d.src_ld + cc] + d.src2[(size_t)r * d.src2_ld + cc];
+    } else if (d.mode == PK_NEGPROJ) {
+      const float rv = i == i0 ? rv0 : d.src[(size_t)r * d.src_ld + cc];
+      const float nrm = nrm_s;
+      float a = rv;
+      if (nrm > 0.98f) a = ((float)0.98994949366116658 * rv) / sqrtf(nrm);
+      a = a + (r == cc ? 0.01f : 0.f);
+      v = -a;
+    } else {
+      const float* src = d.src + (size_t)r * d.src_ld + cc;
+      double sa[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      int k = 0;
+      for (; k + 8 <= d.nslab; k += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) sa[u] += src[(size_t)(k + u) * d.slab_stride];
+      }
+      for (; k < d.nslab; ++k) sa[0] += src[(size_t)k * d.slab_stride];
+      const double s0 = (sa[0] + sa[1]) + (sa[2] + sa[3]), s1 = (sa[4] + sa[5]) + (sa[6] + sa[7]);
+      const double s2 = 0.0, s3 = 0.0;
+      v = d.scale * (float)((s0 + s1) + (s2 + s3));
+    }
+    if (d.dst) {
+      if (d.transpose)
+        d.dst[(size_t)cc * d.dst_ld + r] = v;
+      else
+        d.dst[(size_t)r * d.dst_ld + cc] = v;
+    }
+    if (d.fdst) {
+      const int dr = (d.transpose ? cc : r) + d.frow0, dc = (d.transpose ? r : cc) + d.fcol0;
+      if (d.fsplit) {
+        // v = hi + mid + lo exactly: hi, mid rounded to nearest even, lo the
+        // remainder (phase.hpp split_two)
+        unsigned short* img = (unsigned short*)d.fdst + x3_off(dr, dc, d.ftout);
+        const __bf16 h = (__bf16)v;
+        const float r1 = v - (float)h;
+        const __bf16 m = (__bf16)r1;
+        const float r2 = r1 - (float)m;
+        img[0] = __builtin_bit_cast(unsigned short, h);
+        img[512] = __builtin_bit_cast(unsigned short, m);
+        img[1024] = (unsigned short)(__float_as_uint(r2) >> 16);
+      } else {
+        d.fdst[frag_off(dr, dc, d.ftin, d.ftout)] = v;
+      }
+    }
+  }
+}
+__global__ void __launch_bounds__(256) pack_tagged_kernel(const PackDesc* descs, const float* params, float* grad) {
+  pack_block(descs, blockIdx.y, params, grad);
+}
+// RtR_j = W_j^T W_j (Functions/naisnet.py:33) and per-tile partial sums of
+// squares for the Frobenius norm (fixed order).  One 16x16 output tile per
+// 256-thread workgroup; the whole 16 x L and L x 16 operand strips (L <= 128)
+// are staged in LDS with one round of independent loads (a K-tiled loop would
+// chain L/16 dependent global-load latencies).
+__device__ __forceinline__ void rtr_tile(const float* params, const long long* woffs, int L, float* const* rtr,
+                                         float* const* wsnap, double* part, int nblk, int j, int tile) {
+  __shared__ float As[16][NAIS_LMAX + 1];   // As[r][k] = W[k][16 ti + r]
+  __shared__ float Bs[NAIS_LMAX][17];       // Bs[k][c] = W[k][16 tj + c]
+  const int nt = (L + 15) / 16;
+  const int ti = tile / nt, tj = tile % nt;
+  const float* W = params + woffs[j];
+  // every operand load in one round (a strided loop waited for each load
+  // before the next: ~7 dependent global round trips)
+  constexpr int PER = NAIS_LMAX * 16 / 256;
+  float av[PER], bv[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = threadIdx.x + 256 * u;
+    const int k = e >> 4, q = e & 15;
+    const int ra = 16 * ti + q, cb = 16 * tj + q;
+    av[u] = (k < L && ra < L) ? W[k * L + ra] : 0.f;
+    bv[u] = (k < L && cb < L) ? W[k * L + cb] : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = threadIdx.x + 256 * u;
+    const int k = e >> 4, q = e & 15;
+    if (k < L) {
+      As[q][k] = av[u];
+      Bs[k][q] = bv[u];
+    }
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  float v = 0.f;
+  for (int k = 0; k < L; ++k) v += As[ty][k] * Bs[k][tx];
+  const int row = ti * 16 + ty, col = tj * 16 + tx;
+  // snapshot of W_j before this step's update (one 16 x 16 tile per block):
+  // the fused optimizer update rewrites params while proj_backward_kernel's
+  // other blocks still read W_j
+  if (row < L && col < L) wsnap[j][row * L + col] = W[row * L + col];
+  double sq = 0.0;
+  if (row < L && col < L) {
+    rtr[j][row * L + col] = v;
+    sq = (double)v * (double)v;
+  }
+  __shared__ double red[256];
+  red[threadIdx.x] = sq;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[j * nblk + tile] = red[0];
+}
+__global__ void __launch_bounds__(256) rtr_params_kernel(const float* params, const long long* woffs, int L,
+                                                         float* const* rtr, float* const* wsnap, double* part, int nblk) {
+  rtr_tile(params, woffs, L, rtr, wsnap, part, nblk, blockIdx.y, blockIdx.x);
+}
+// NAIS projection adjoint (Functions/naisnet.py:30-39 reversed), one kernel:
+//   Abar_j = dL/dA_j (slab sums), R_j = W_j^T W_j, n = |R_j|_F
+//   Rbar   = c n^-1/2 (Abar - 1/2 <Abar, R> R / n^2)  (Q4 branch taken, c = sqrt 0.98)
+//          = Abar                                     (not taken)
+//   Wbar_j = W_j (Rbar + Rbar^T)  -> grad
+// Every block recomputes <Abar_j, R_j> in the same fixed order (L^2 products,
+// cheap), so no separate reduction launch is needed; S = Rbar + Rbar^T is
+// formed on the fly in the B tile of the LDS-tiled GEMM.
+__global__ void __launch_bounds__(256) proj_backward_kernel(const float* const* wsnap, const long long* woffs,
+                                                            float* const* abar, float* const* rtr, int L,
+                                                            const double* proj_part, int proj_n, const double* dot_part,
+                                                            int dot_nblk, int dot_nused, float* grad, FusedOpt fo,
+                                                            int fuse) {
+  __shared__ float As[16][NAIS_LMAX + 1];   // As[r][k] = W[16 ti + r][k]
+  __shared__ float Bs[NAIS_LMAX][17];       // Bs[k][c] = S[k][16 tj + c], S = Rbar + Rbar^T
+  __shared__ double dot_s, nrm_s;
+  const int j = blockIdx.y, nt = (L + 15) / 16;
+  const int ti = blockIdx.x / nt, tj = blockIdx.x % nt;
+  const float* Ab = abar[j];
+  const float* R = rtr[j];
+  // W_j from the snapshot rtr_params_kernel took: with the fused update, the
+  // blocks (ti, tj') of this launch rewrite params' W_j rows in place while
+  // this block still reads them
+  const float* W = wsnap[j];
+  // every operand load in one round, before the scalars are known
+  constexpr int PER = NAIS_LMAX * 16 / 256;
+  float wv[PER], abs_[PER], rs[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = threadIdx.x + 256 * u;
+    const int k = e >> 4, q = e & 15;
+    const int ra = 16 * ti + q, cb = 16 * tj + q;
+    const bool in = k < L;
+    wv[u] = (in && ra < L) ? W[ra * L + k] : 0.f;
+    const bool ok = in && cb < L;
+    abs_[u] = ok ? Ab[k * L + cb] + Ab[cb * L + k] : 0.f;
+    rs[u] = ok ? R[k * L + cb] + R[cb * L + k] : 0.f;
+  }
+  // this thread's parameter / moments for the fused update, in the same round
+  const int row = ti * 16 + (threadIdx.x >> 4), col = tj * 16 + (threadIdx.x & 15);
+  const bool own = row < L && col < L;
+  const long long gi_idx = own ? woffs[j] + row * L + col : 0;
+  OptVals pv{};
+  if (fuse && own) pv = opt_load(gi_idx, fo.prm, fo.m, fo.v);
+  // the optimizer scalars while the operand loads are in flight
+  if (fuse) fused_opt_prologue(fo, false);
+  if (threadIdx.x < 64) {   // <Abar_j, R_j> from the finalize partials, fixed-order butterfly
+    double dsum = 0.0;
+    for (int b = threadIdx.x; b < dot_nused; b += 64) dsum += dot_part[(size_t)j * dot_nblk + b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) dsum += __shfl_xor(dsum, o);
+    // |R_j|_F from the rtr partials (proj_n <= 64), the phase kernels' order
+    const double nrm = nais_norm_from(threadIdx.x < proj_n ? proj_part[(size_t)j * proj_n + threadIdx.x] : 0.0);
+    if (threadIdx.x == 0) {
+      dot_s = dsum;
+      nrm_s = nrm;
+    }
+  }
+  __syncthreads();
+  const double dot = dot_s;
+  const double n = nrm_s;
+  const bool taken = (float)n > 0.98f;
+  const float cA = taken ? (float)(0.98994949366116658 / sqrt(n)) : 1.f;
+  const float cR = taken ? (float)(0.98994949366116658 / sqrt(n) * 0.5 * dot / (n * n)) : 0.f;
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = threadIdx.x + 256 * u;
+    const int k = e >> 4, q = e & 15;
+    if (k < L) {
+      As[q][k] = wv[u];
+      Bs[k][q] = cA * abs_[u] - cR * rs[u];
+    }
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  float acc = 0.f;
+  for (int k = 0; k < L; ++k) acc += As[ty][k] * Bs[k][tx];
+  if (own) {
+    grad[gi_idx] = acc;
+    if (fuse) opt_apply(fo.a, gi_idx, acc, pv, fo.prm, fo.m, fo.v);
+  }
+}
 #endif
 
 }  // namespace dbsde

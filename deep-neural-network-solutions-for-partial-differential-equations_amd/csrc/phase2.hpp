@@ -37,7 +37,7 @@ template <int T, int TD, int K, int ACT, bool HV, int NT, int NBUF, bool ADOT>
 __global__ void __launch_bounds__(64 * P3_WAVES, 1) phaseC2_kernel(FusedArgs p);
 
 // the instantiations phase2.hip builds (its own translation unit, compiled in
-// parallel with engine.hip): config 4's FC [101,256x4,1] and config 1's FC
+// parallel with step.hip): config 4's FC [101,256x4,1] and config 1's FC
 // [2,256x4,1] (call_option_1d.py), one tile per wave, 48 KiB pieces, adot
 // through memory.  (The width-112 networks with two tiles
 // per wave, X(7, 7, 3, ACT, HV, 2, 4, ADOT), measured slower than phase.hpp's

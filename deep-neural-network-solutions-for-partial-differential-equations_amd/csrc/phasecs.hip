@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 // device helpers of kernels.hpp / fused.hpp only: their non-template kernels
-// are defined once, in engine.hip
+// are defined once, in step.hip
 #define DBSDE_DEVICE_HELPERS_ONLY
 #include "phasecs.hpp"
 

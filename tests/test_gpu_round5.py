@@ -95,7 +95,7 @@ def test_stream_order_by_events_matches_value_ops(pkg, dev):
 def test_held_back_prefetch_on_the_second_stream_is_the_same_step(pkg, dev):
     """At the north-star shape the step runs the two-stream pipeline, so a
     prefetched batch is held back and rolled out on the step's second stream
-    after its weight-gradient slices (engine.hip launch_deferred_on): four
+    after its weight-gradient slices (rollout.hip launch_deferred_on): four
     device steps with the next batch prefetched end on the same parameters
     bit for bit as four without prefetching; a prefetch that no step consumes
     (a different seed) leaves the steps unchanged as well."""

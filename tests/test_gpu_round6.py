@@ -2,7 +2,7 @@
 
   * a prefetched batch no step consumes ("stale": prefetch seed X, run seed Y,
     repeat) must never be rolled out into the path buffer the running step
-    reads (engine.hip launch_deferred_on falls back to pf_stream avoiding that
+    reads (rollout.hip launch_deferred_on falls back to pf_stream avoiding that
     buffer): the X / Y / Z exports, loss and gradient of every step equal a
     context without prefetching, bit for bit, at the north-star shape (two
     path chunks, so the held-back rollout runs on the second stream);
@@ -10,8 +10,12 @@
     (dbsde_set_stream follows torch's current stream): the context orders the
     new stream after the old one on every switch, and a prefetched rollout
     joined into one stream is waited for by a consumer on another
-    (engine.hip wait_pending), so the steps equal the single-stream,
-    unprefetched ones bit for bit."""
+    (rollout.hip wait_pending), so the steps equal the single-stream,
+    unprefetched ones bit for bit;
+  * dropping the prefetches (prefetch_drop, an in-place Xi change, a new
+    Cholesky factor) after a rollout was held back and issued on the second
+    chunk stream: the next steps equal a twin that never prefetched, bit for
+    bit (rollout.hip drop_all orders the stream after every pending rollout)."""
 import os
 
 import numpy as np
@@ -157,3 +161,93 @@ def test_large_batch_is_the_sum_of_its_halves(pkg, dev, g):
     assert float(full["loss"]) == pytest.approx(float(a["loss"] + b["loss"]), rel=1e-5)
     g2 = a["grad"] + b["grad"]
     torch.testing.assert_close(full["grad"], g2, rtol=0, atol=2e-5 * float(g2.abs().max()))
+
+
+# ---- dropping prefetches after a held-back rollout went to the second chunk stream
+def _two_chunk_model(pkg, dev, monkeypatch, Xi, Ms, Ns, layers, params=None):
+    """A NAIS-Net / Sine model whose context takes DBSDE_CHUNKS=2 at creation."""
+    with monkeypatch.context() as mp:
+        mp.setenv("DBSDE_CHUNKS", "2")
+        torch.manual_seed(6)
+        m = pkg.BlackScholesBarenblatt(Xi, 1.0, Ms, Ns, layers[0] - 1, layers, "NAIS-Net", "Sine", device=dev)
+    if params is not None:
+        m.params.copy_(torch.from_numpy(params).to(dev))
+    return m
+
+
+def _steps_with_a_drop(m, prefetch, between, seed2):
+    """device_step(seed=1[, next_seed=2]); between(m); device_step(seed=seed2):
+    the second loss and the final parameters."""
+    opt = m.new_optimizer_state("Adam", 1e-3)
+    m.device_step(opt, 1e-3, seed=1, next_seed=2 if prefetch else None)
+    between(m)               # no synchronisation: the ordering is what is tested
+    loss = m.device_step(opt, 1e-3, seed=seed2).clone()
+    torch.cuda.synchronize()
+    return loss.cpu(), m.params.detach().cpu().clone()
+
+
+@pytest.mark.parametrize("how", ["prefetch_drop", "xi_in_place"])
+def test_drop_after_a_held_back_rollout(pkg, dev, g, monkeypatch, how):
+    """North-star layers and parameters at M = 256, N = 5 with DBSDE_CHUNKS=2:
+    the step is the piped two-chunk one, so the prefetch of seed 2 is held back
+    and rolled out on the second chunk stream (pipe2) after the join, where
+    nothing orders the caller's stream after it.  Dropping it (prefetch_drop,
+    or the in-place Xi change that makes device_step drop it) must leave the
+    next step, whose in-step rollout may take that buffer and whose Xi copy
+    is rewritten, equal to a twin that never prefetched: loss and parameters
+    bit for bit.
+
+    That the held-back rollout goes to pipe2 here, from loss_grad_impl's
+    conditions (step.hip): R = Rp = 256 * 6 = 1536; the layout is the
+    wave-tile one (NAIS, Wp = Dp = 112, K = 3), the step is unprofiled and
+    has a gradient; the phase variant has 16, 64 or 128 rows per workgroup,
+    256 paths are 16, 4 or 2 such units, an even count, so nch = 2 stays; the
+    chunk boundary is row (256 / 2) * 6 = 768 whichever the variant; with
+    S = 128 slices over n32 = 1536 / 32 = 48 row steps, slice k starts at row
+    32 * floor(48 k / 128), which is 768 first at k = 64, a multiple of 8: so
+    tnw_piped holds and launch_deferred_on(pipe2) runs, with the other path
+    buffer free (first step)."""
+    layers = [int(v) for v in g["layers"]]
+
+    def between(m):
+        if how == "prefetch_drop":
+            m.solver.prefetch_drop()
+        else:
+            m.Xi.mul_(1.5)
+
+    runs = [_steps_with_a_drop(_two_chunk_model(pkg, dev, monkeypatch, g["Xi"], 256, 5, layers, g["params"]),
+                               prefetch, between, 3) for prefetch in (True, False)]
+    assert torch.isfinite(runs[1][0]).all() and torch.isfinite(runs[1][1]).all()
+    torch.testing.assert_close(runs[0][0], runs[1][0], rtol=0, atol=0)
+    torch.testing.assert_close(runs[0][1], runs[1][1], rtol=0, atol=0)
+
+
+@pytest.mark.parametrize("seed2", [2, 3])
+def test_set_corr_after_a_held_back_correlated_rollout(pkg, dev, monkeypatch, seed2):
+    """The same with Cholesky-correlated increments (dbsde_set_corr) and a new
+    factor between the steps: the held-back rollout of seed 2 read the old
+    factor, so it is dropped (seed2 = 2: the step must not consume it) and
+    waited for before the factor's memory is rewritten (seed2 = 3: nor may its
+    buffer be reused while it runs).
+
+    The smallest two-chunk piped shape: the wave-tile weight gradient needs a
+    NAIS net with Wp == Dp, whose smallest fused variant is width 16 (D <= 14;
+    D = 2 is the smallest with a correlation to speak of), 64 rows per
+    workgroup and no column-split form; two chunks of whole 64-path units
+    need M = 128.  At N = 5, Rp = 768, the chunk boundary is row 384 and slice
+    64 of 128 starts at row 32 * floor(24 * 64 / 128) = 384."""
+    D, Ms, Ns = 2, 128, 5
+    layers = [D + 1, 16, 16, 16, 16, 1]
+    Xi = np.array([[1.0, 0.5]], dtype=np.float32)
+    L1 = np.linalg.cholesky(np.array([[1.0, 0.5], [0.5, 1.0]]))
+    L2 = np.linalg.cholesky(np.array([[1.0, -0.3], [-0.3, 1.0]]))
+
+    def run(prefetch):
+        m = _two_chunk_model(pkg, dev, monkeypatch, Xi, Ms, Ns, layers)
+        m.solver.set_corr(L1)
+        return _steps_with_a_drop(m, prefetch, lambda mm: mm.solver.set_corr(L2), seed2)
+
+    with_pf, twin = run(True), run(False)
+    assert torch.isfinite(twin[0]).all() and torch.isfinite(twin[1]).all()
+    torch.testing.assert_close(with_pf[0], twin[0], rtol=0, atol=0)
+    torch.testing.assert_close(with_pf[1], twin[1], rtol=0, atol=0)

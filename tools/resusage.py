@@ -1,7 +1,7 @@
 """Per-kernel register / scratch / occupancy summary of one translation unit
 (hipcc -Rpass-analysis=kernel-resource-usage), demangled, one line per kernel.
 
-    python tools/resusage.py csrc/engine.hip [name-filter ...]
+    python tools/resusage.py csrc/step.hip [name-filter ...]
 """
 import re
 import subprocess

@@ -2,7 +2,7 @@
 bench.py's event records: `fused_phases_pipelined` = first phaseA start to
 last phaseC end of each step (the two path chunks on two streams overlap, so
 their per-kernel durations do not add up to the section).  In unprofiled
-steps each chunk's weight-gradient slices run inside that span (engine.hip
+steps each chunk's weight-gradient slices run inside that span (step.hip
 tnw_piped), so the trace span of those steps is the phases plus the overlap.
 Trace a `bench.py --full` run: only that one has the event-profiled steps.
 
