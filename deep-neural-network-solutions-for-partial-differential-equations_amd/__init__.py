@@ -14,8 +14,8 @@ from . import _lib
 from .deepbsde import BlackScholesBarenblatt, u_exact
 from .fbsnn import FBSNN, PredictionGenerator
 from .problems import BasketCallOption, BSPDETestCase, CallOption, CallOption1D, HamiltonJacobiBellman, HestonFBSNN
-from .solver import NativeSolver, ProblemSpec, exact, hjb_mc
+from .solver import NativeSolver, ProblemSpec, exact, hjb_mc, mc_value
 
 __all__ = ["FBSNN", "PredictionGenerator", "BlackScholesBarenblatt", "u_exact", "CallOption", "CallOption1D",
            "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman", "HestonFBSNN", "NativeSolver",
-           "ProblemSpec", "exact", "hjb_mc", "_lib"]
+           "ProblemSpec", "exact", "hjb_mc", "mc_value", "_lib"]

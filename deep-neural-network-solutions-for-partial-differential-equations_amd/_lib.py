@@ -28,6 +28,7 @@ EXPORTED = [
     "dbsde_param_count", "dbsde_param_used_mask", "dbsde_matrix_form", "dbsde_brownian_dim", "dbsde_set_corr", "dbsde_brownian", "dbsde_prefetch",
     "dbsde_prefetch_cancel",
     "dbsde_loss_grad", "dbsde_net_u", "dbsde_net_u_vjp", "dbsde_net_u_xvjp", "dbsde_optimizer_step", "dbsde_exact", "dbsde_hjb_mc",
+    "dbsde_mc_value",
     "dbsde_profile_enable", "dbsde_profile_count", "dbsde_profile_read", "dbsde_profile_reset",
     "dbsde_vec_reduce", "dbsde_vec_axpby", "dbsde_lbfgs_direction", "dbsde_train_step",
     "dbsde_stream_order_by_events",
@@ -101,6 +102,8 @@ def load():
         "dbsde_prefetch_cancel": (i, [vp]),
         "dbsde_exact": (i, [i, vp, vp, ll, i, ctypes.c_float, vp, vp, vp, vp]),
         "dbsde_hjb_mc": (i, [vp, vp, i, i, ctypes.c_float, ll, ctypes.c_ulonglong, vp, vp]),
+        "dbsde_mc_value": (i, [ctypes.POINTER(Problem), i, ctypes.c_float, vp, vp, vp, i, i, ll, ctypes.c_ulonglong,
+                               ctypes.c_ulonglong, vp, vp, vp, vp]),
         "dbsde_loss_grad": (i, [vp, vp, ctypes.POINTER(Batch), vp, ctypes.POINTER(Outputs)]),
         "dbsde_net_u": (i, [vp, vp, i, vp, vp, vp, vp]),
         "dbsde_net_u_vjp": (i, [vp, vp, i, vp, vp, vp, vp, vp]),

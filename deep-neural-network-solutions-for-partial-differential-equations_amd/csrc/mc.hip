@@ -1,0 +1,514 @@
+// mc.hip -- Feynman-Kac Monte-Carlo comparator for every linear problem
+// (dbsde_mc_value, include/dbsde.h).  The device counterpart of the reference
+// drivers' Monte-Carlo pricers (with_corr...py:1283-1325 generate_paths /
+// monte_carlo_price, basket_pricer.py, numerics/multidimensional_mc_pricer.py,
+// numerics/heston_closed_form_ii.py:6-83), simulating the problem's OWN SDE.
+//
+// Mathematics.  A dbsde_problem with phi_zz == 0 has phi = phi_r (Y - phi_c X.Z),
+// so the BSDE the step trains on is the linear PDE
+//   u_t + (mu + phi_r phi_c X).Du + 1/2 tr(sigma sigma^T D^2 u) - phi_r u = 0,  u(T, .) = g,
+// whose solution is  u(t, x) = E[ exp(-phi_r tau) g(X~_T) | X~_t = x ],  tau = T - t,
+// X~ following the problem's Euler scheme with drift coefficient
+// mu_eff = mu_a + phi_r phi_c (fp32, computed once).  Check: BSB has mu = 0,
+// sigma = 0.4 X, phi = r (Y - X.Z): exp((r + sigma^2) tau) |x|^2 = DBSDE_EXACT_BSB.
+// Heston has phi_c = 0 and its own drift and 2x2 blocks, stepped exactly as
+// rollout_heston_kernel steps them.  phi_zz != 0 (HJB) is not linear: dbsde_hjb_mc.
+//
+// Draws.  The normals of sample k, step n, Brownian coordinate d are
+// philox_normal4(seed, offset, k, n >> 2, d)[n & 3] -- the device-mode rollout's
+// keying for global path k -- for EVERY point of a call (common random numbers).
+// Point p runs the training grid with T replaced by tau_p = fp32(T) - t_p:
+// t_n = fp32(fp64 cumsum of tau_p / n_steps), dt_n their fp32 differences,
+// sqdt = sqrtf(tau_p / n_steps); the state is fp32 and the step is the
+// reference-order, non-contracted step of paths.hpp.
+//
+// Layout.  A thread owns (sample k, coordinate d) and carries the state -- and
+// the tangent J when delta is asked for -- of a tile of MC_PT points in
+// registers: one Philox block + Box-Muller per four steps serves all of them.
+// Per-point dt_n / sqdt come from a small table (mc_grid_kernel) through
+// wave-uniform loads.  A 256-thread workgroup holds S = min(32, 256 / nd)
+// samples side by side (nd = D, or k for Heston); it owns one chunk of the
+// samples (grid.y) and one tile of points (grid.x).  After the last step each
+// thread puts its payoff term (X or X^2 of the g_cols columns) into LDS, thread
+// (sample, point) sums a sample's nd terms in a fixed order, forms g and
+// dg/da in fp64 and accumulates sum g, sum g^2; the (k, d) threads accumulate
+// dg/dX_d J_d in fp64 registers.  At the end of the chunk the S samples are
+// summed in LDS in a fixed order into the partials buffer
+// [P][chunks][2 (+ D)] (hipMallocAsync); mc_final_kernel sums the chunks in
+// order.  No floating-point atomics: the result is bitwise repeatable, and a
+// point's result depends on neither P nor its index (the chunking is a
+// function of mc and nd alone, the slots of a tile run the same code).
+// nd > 256 (S = 1): a thread runs its coordinates d = tid + 256 j one after
+// the other; with delta it runs them a second time once dg/da is known and
+// accumulates into its own partials slots.
+// Correlated (DIAG, nb <= 128): the lower triangle of L sits packed in LDS
+// (33 KB); per four-step block the workgroup's normals Z [nd][4 S] go through
+// LDS, L . Z runs as v_mfma_f32_16x16x4_f32 tiles over the four waves (the
+// lower triangle only) and returns through LDS to the (k, d) threads: one
+// product per four steps, shared by the tile's points and scaled by each
+// point's sqdt afterwards.
+// Nothing per path goes to HBM.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/dbsde.h"
+#include "philox.hpp"
+#include "rn.hpp"
+
+struct dbsde_ctx;
+int fail(dbsde_ctx* c, int code, const std::string& msg);   // net.hip
+
+namespace dbsde {
+
+constexpr int MC_PT = 8;           // points per thread tile
+constexpr int MC_THREADS = 256;
+constexpr int MC_SMAX = MC_THREADS / MC_PT;   // samples per workgroup pass (one reducing thread per (sample, point))
+constexpr int MC_CHUNKS = 256;     // sample chunks (grid.y) at most
+constexpr int MC_DMAX = 4096;
+constexpr int MC_NBMAX = 128;      // correlated: L in LDS
+constexpr int MC_LPACK = MC_NBMAX * (MC_NBMAX + 1) / 2;
+constexpr int MC_ZMAX = 2048;       // correlated: floats of the Z (and C) tile, nd x (4 S padded to 16) <= 2048
+enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2 };
+
+typedef float mcf4 __attribute__((ext_vector_type(4)));
+
+struct McArgs {
+  int D, nd, P, Ppad, n_steps;
+  int S, nj, nch, W;               // samples per pass, coordinate passes, chunks, partials row width
+  int g_kind, gcols;
+  float strike, g_alpha, phi_r, T;
+  float mu, sig_a, sig_b;          // DIAG: mu = mu_eff
+  float kappa, theta, hsig, rho;   // Heston (mu = mu_a)
+  long long mc, per;               // samples, samples per chunk
+  unsigned long long seed, offset;
+  const float* t;                  // [P]
+  const float* x;                  // [P, D]
+  const float* L;                  // [nd, nd] or null
+  float* dtab;                     // [n_steps, Ppad]
+  float* sqdt;                     // [Ppad]
+  float* Lp;                       // packed lower triangle of L^T: row j holds L[d][j], d = j .. nd - 1
+  double* part;                    // [P, nch, W]
+};
+
+__device__ __forceinline__ int mc_lp_off(int j, int nd) { return j * nd - (j * (j - 1)) / 2; }
+
+// per-point time grid (tau <= 0: a zero grid, the state stays at x) and the
+// packed L
+__global__ void __launch_bounds__(256) mc_grid_kernel(McArgs a) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  if (gid < a.Ppad) {
+    const int pc = gid < a.P ? gid : a.P - 1;
+    const float tau = rn_sub(a.T, a.t[pc]);
+    const bool run = tau > 0.f;
+    const double dt64 = run ? (double)tau / (double)a.n_steps : 0.0;
+    a.sqdt[gid] = run ? sqrtf(tau / (float)a.n_steps) : 0.f;
+    double tacc = 0.0;
+    float t0 = 0.f;
+    for (int n = 0; n < a.n_steps; ++n) {
+      tacc += dt64;
+      const float t1 = (float)tacc;
+      a.dtab[(size_t)n * a.Ppad + gid] = rn_sub(t1, t0);
+      t0 = t1;
+    }
+  }
+  if (a.L)
+    for (int e = gid; e < a.nd * a.nd; e += gridDim.x * 256) {
+      const int d = e / a.nd, j = e - d * a.nd;
+      if (j <= d) a.Lp[mc_lp_off(j, a.nd) + d - j] = a.L[e];
+    }
+}
+
+__device__ __forceinline__ bool mc_squares(int g_kind) { return g_kind == DBSDE_G_SUMSQ || g_kind == DBSDE_G_LOG; }
+
+// g and dg/d(sum) from the sum of the payoff terms (X or X^2) of a sample;
+// dg/dX_d = gp * (2 X_d or 1).  The call payoffs use 1/2 at a == 0, as bs_call
+// (evals.hip) does.
+__device__ __forceinline__ void mc_payoff(int g_kind, double s, double cols, double K, double alpha, double& g,
+                                          double& gp) {
+  if (g_kind == DBSDE_G_SUMSQ) {
+    g = s;
+    gp = 1.0;
+  } else if (g_kind == DBSDE_G_LOG) {
+    const double q = 0.5 + 0.5 * s;
+    g = log(q);
+    gp = 0.5 / q;
+  } else if (g_kind == DBSDE_G_SMOOTH_CALL) {
+    const double a = s / cols - K, sg = 1.0 / (1.0 + exp(-alpha * a));
+    g = a * sg;
+    gp = (sg + a * alpha * sg * (1.0 - sg)) / cols;
+  } else {
+    const double c = g_kind == DBSDE_G_CALL_MEAN ? cols : 1.0;
+    const double a = s / c - K;
+    g = a > 0.0 ? a : 0.0;
+    gp = (a > 0.0 ? 1.0 : (a == 0.0 ? 0.5 : 0.0)) / c;
+  }
+}
+
+// The whole path of sample k, thread coordinate d, for the tile's MC_PT
+// points.  DIAG / CORR: X the state, V the tangent J (DELTA).  HESTON: X = S_d,
+// V = v_d.  s: the thread's sample slot, act: the thread owns a (sample,
+// coordinate) pair.  Every thread of the workgroup calls this (CORR has
+// barriers inside).
+template <int KIND, bool DELTA>
+__device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int s, bool act, int p0,
+                                        const float (&sq)[MC_PT], float (&X)[MC_PT], float (&V)[MC_PT], float* zs,
+                                        const float* Ls) {
+  for (int n0 = 0; n0 < a.n_steps; n0 += 4) {
+    float z[4];
+    philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)d, z);
+    if constexpr (KIND == MC_CORR) {
+      // dW^T = L . Z on the matrix cores.  Z [nd][NCp]: row j = coordinate, column
+      // 4 s + i = step i of sample slot s (NCp = the 4 S columns padded to 16).
+      // One v_mfma_f32_16x16x4_f32 per (16-row block o of L, 16-column block cb,
+      // K-step t): A = L[16 o + cl][4 t + q] from the packed triangle, B =
+      // Z[4 t + q][16 cb + cl]; L is lower triangular, so block o stops at
+      // t < 4 o + 4.  Tiles go round-robin over the four waves; the products
+      // C [nd][NCp] return through LDS to the (sample, coordinate) threads.
+      const int NC = 4 * a.S, NCp = (NC + 15) & ~15;
+      float* cs = zs + MC_ZMAX;
+      if (act) *(mcf4*)(zs + d * NCp + 4 * s) = mcf4{z[0], z[1], z[2], z[3]};
+      __syncthreads();
+      {
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int lane = threadIdx.x & 63, cl = lane & 15, q = lane >> 4;
+        const int ncb = NCp >> 4, ntile = ((a.nd + 15) >> 4) * ncb, nt4 = (a.nd + 3) >> 2;
+        for (int tl = wave; tl < ntile; tl += MC_THREADS / 64) {
+          const int o = tl / ncb, cb = tl - o * ncb;
+          const int drow = 16 * o + cl, col = 16 * cb + cl;
+          const int tmax = 4 * o + 4 < nt4 ? 4 * o + 4 : nt4;
+          const bool rok = drow < a.nd, cok = col < NC;
+          auto la = [&](int t) {   // k <= drow < nd: inside the packed triangle
+            const int k = 4 * t + q;
+            return (rok && k <= drow) ? Ls[mc_lp_off(k, a.nd) + drow - k] : 0.f;
+          };
+          auto zb = [&](int t) {
+            const int k = 4 * t + q;
+            return (cok && k < a.nd) ? zs[k * NCp + col] : 0.f;
+          };
+          mcf4 acc0 = mcf4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;   // two chains: the accumulator latency
+          int t = 0;
+          for (; t + 1 < tmax; t += 2) {
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(la(t), zb(t), acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(la(t + 1), zb(t + 1), acc1, 0, 0, 0);
+          }
+          if (t < tmax) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(la(t), zb(t), acc0, 0, 0, 0);
+          acc0 += acc1;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = 16 * o + 4 * q + r;
+            if (row < a.nd) cs[row * NCp + col] = acc0[r];
+          }
+        }
+      }
+      __syncthreads();
+      const mcf4 c = *(const mcf4*)(cs + d * NCp + 4 * s);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) z[i] = c[i];
+    }
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      if (n0 + kk >= a.n_steps) break;
+      const float* dtr = a.dtab + (size_t)(n0 + kk) * a.Ppad + p0;   // wave-uniform
+#pragma unroll
+      for (int i = 0; i < MC_PT; ++i) {
+        const float dt = dtr[i];
+        const float w = rn_mul(sq[i], z[kk]);
+        if constexpr (KIND == MC_HESTON) {
+          const float S = X[i], v = V[i];
+          const float muS = clamp100(rn_mul(a.mu, S));
+          const float muV = clamp100(rn_mul(a.kappa, rn_sub(a.theta, v)));
+          const float sv = sqrtf(fmaxf(v, 1e-8f));
+          const float sigS = rn_mul(sv, S), sigV = rn_mul(a.hsig, sv);
+          const float d00 = clamp100(sigS), d11 = clamp100(sigV);
+          const float d01 = clamp100(rn_mul(a.rho, sigV)), d10 = clamp100(rn_mul(a.rho, sigS));
+          X[i] = rn_add(rn_add(S, rn_mul(muS, dt)), rn_mul(rn_add(d00, d01), w));
+          V[i] = rn_add(rn_add(v, rn_mul(muV, dt)), rn_mul(rn_add(d10, d11), w));
+        } else {
+          const float x = X[i];
+          const float sg = rn_add(rn_mul(a.sig_a, x), a.sig_b);
+          X[i] = rn_add(rn_add(x, rn_mul(rn_mul(a.mu, x), dt)), rn_mul(sg, w));
+          if constexpr (DELTA) {
+            const float J = V[i];
+            V[i] = rn_add(rn_add(J, rn_mul(rn_mul(a.mu, J), dt)), rn_mul(rn_mul(a.sig_a, J), w));
+          }
+        }
+      }
+    }
+  }
+  if constexpr (KIND == MC_CORR) __syncthreads();   // the C tile shares LDS with what the caller writes next
+}
+
+template <int KIND, bool DELTA>
+__global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
+  __shared__ __attribute__((aligned(16))) double fred[MC_PT * MC_THREADS];
+  __shared__ float gpl[MC_THREADS];
+  // correlated: Z and C of mc_path share fred's 16 KB (fred is written only after a
+  // path's last barrier and read before the next path's first)
+  static_assert(sizeof(fred) >= 2 * MC_ZMAX * sizeof(float), "Z and C tiles must fit fred");
+  float* zs = reinterpret_cast<float*>(fred);
+  __shared__ float Ls[KIND == MC_CORR ? MC_LPACK : 1];
+  const int tid = threadIdx.x;
+  const int p0 = blockIdx.x * MC_PT, ch = blockIdx.y;
+  const int nd = a.nd, S = a.S, nj = a.nj;
+  if constexpr (KIND == MC_CORR)
+    for (int e = tid; e < nd * (nd + 1) / 2; e += MC_THREADS) Ls[e] = a.Lp[e];   // read after mc_path's first barrier
+  const bool act = nj > 1 || tid < S * nd;
+  const int s = (act && nj == 1) ? tid / nd : 0;
+  const int d0 = act ? (nj > 1 ? tid : tid - s * nd) : 0;
+  const int RW = nj > 1 ? MC_THREADS : nd;            // LDS entries of one sample's payoff terms
+  const int rs = tid / MC_PT, ri = tid - rs * MC_PT;  // reducing role: sample slot rs, point slot ri
+  const bool reducer = rs < S;
+  const bool squares = mc_squares(a.g_kind);
+  const double cols = (double)a.gcols, K = (double)a.strike, alpha = (double)a.g_alpha;
+  float sq[MC_PT];
+  int pc[MC_PT];
+#pragma unroll
+  for (int i = 0; i < MC_PT; ++i) {
+    sq[i] = a.sqdt[p0 + i];
+    pc[i] = p0 + i < a.P ? p0 + i : a.P - 1;
+  }
+  const long long k0 = (long long)ch * a.per, k1 = k0 + a.per < a.mc ? k0 + a.per : a.mc;
+  double gs = 0.0, g2 = 0.0;
+  double dacc[MC_PT];
+#pragma unroll
+  for (int i = 0; i < MC_PT; ++i) dacc[i] = 0.0;
+
+  for (long long kb = k0; kb < k1; kb += S) {
+    const long long kk = kb + s;
+    const bool live = act && kk < k1;
+    float X[MC_PT], V[MC_PT];
+    double fs[MC_PT];
+#pragma unroll
+    for (int i = 0; i < MC_PT; ++i) fs[i] = 0.0;
+    for (int j = 0; j < nj; ++j) {
+      const int d = d0 + MC_THREADS * j;
+      const bool dl = live && d < nd;
+      const int dd = dl ? d : 0;
+#pragma unroll
+      for (int i = 0; i < MC_PT; ++i) {
+        X[i] = a.x[(size_t)pc[i] * a.D + dd];
+        V[i] = KIND == MC_HESTON ? a.x[(size_t)pc[i] * a.D + nd + dd] : 1.f;
+      }
+      mc_path<KIND, DELTA>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls);
+      if (dl) {
+#pragma unroll
+        for (int i = 0; i < MC_PT; ++i) {
+          if (dd < a.gcols) fs[i] += squares ? (double)X[i] * (double)X[i] : (double)X[i];
+          if (KIND == MC_HESTON && nd + dd < a.gcols)
+            fs[i] += squares ? (double)V[i] * (double)V[i] : (double)V[i];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MC_PT; ++i) fred[i * MC_THREADS + tid] = fs[i];
+    __syncthreads();
+    if (reducer) {
+      const double* fr = fred + ri * MC_THREADS + rs * RW;
+      double sum = 0.0;
+      for (int e = 0; e < RW; ++e) sum += fr[e];
+      double g, gp;
+      mc_payoff(a.g_kind, sum, cols, K, alpha, g, gp);
+      if (kb + rs < k1) {
+        gs += g;
+        g2 += g * g;
+      }
+      gpl[tid] = (float)gp;
+    }
+    __syncthreads();
+    if constexpr (DELTA) {
+      for (int j = 0; j < nj; ++j) {
+        const int d = d0 + MC_THREADS * j;
+        const bool dl = live && d < nd;
+        const int dd = dl ? d : 0;
+        if (nj > 1) {   // the coordinates of a long state are run again now that dg/da is known
+#pragma unroll
+          for (int i = 0; i < MC_PT; ++i) {
+            X[i] = a.x[(size_t)pc[i] * a.D + dd];
+            V[i] = 1.f;
+          }
+          mc_path<KIND, DELTA>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls);
+        }
+        if (!dl) continue;
+#pragma unroll
+        for (int i = 0; i < MC_PT; ++i) {
+          const double fp = dd < a.gcols ? (squares ? 2.0 * (double)X[i] : 1.0) : 0.0;
+          const double v = (double)gpl[s * MC_PT + i] * fp * (double)V[i];
+          if (nj == 1) {
+            dacc[i] += v;
+          } else if (p0 + i < a.P) {   // the thread's own slot: first sample stores, the others add
+            double* q = a.part + ((size_t)(p0 + i) * a.nch + ch) * a.W + 2 + dd;
+            *q = kb == k0 ? v : *q + v;
+          }
+        }
+      }
+    }
+  }
+
+  // the chunk's sums over the S sample slots, fixed order
+  if (reducer) {
+    fred[tid] = gs;
+    fred[MC_THREADS + tid] = g2;
+  }
+  __syncthreads();
+  if (tid < MC_PT && p0 + tid < a.P) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int r = 0; r < S; ++r) {
+      s1 += fred[r * MC_PT + tid];
+      s2 += fred[MC_THREADS + r * MC_PT + tid];
+    }
+    double* q = a.part + ((size_t)(p0 + tid) * a.nch + ch) * a.W;
+    q[0] = s1;
+    q[1] = s2;
+  }
+  if constexpr (DELTA) {
+    if (nj == 1) {
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < MC_PT; ++i) fred[i * MC_THREADS + tid] = dacc[i];   // 0 from threads without a pair
+      __syncthreads();
+      for (int e = tid; e < MC_PT * nd; e += MC_THREADS) {
+        const int i = e / nd, d = e - i * nd;
+        if (p0 + i >= a.P) continue;
+        double sum = 0.0;
+        for (int r = 0; r < S; ++r) sum += fred[i * MC_THREADS + r * nd + d];
+        a.part[((size_t)(p0 + i) * a.nch + ch) * a.W + 2 + d] = sum;
+      }
+    }
+  }
+}
+
+// value, standard error and delta of point p (blockIdx.x) from the chunk
+// partials; column c = 0: value / standard error, c >= 1: delta[c - 1]
+__global__ void __launch_bounds__(256) mc_final_kernel(McArgs a, float* value, float* stderr_, float* delta) {
+  const int p = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (c > (delta ? a.D : 0)) return;
+  const float tau = rn_sub(a.T, a.t[p]);
+  const float* xp = a.x + (size_t)p * a.D;
+  const bool squares = mc_squares(a.g_kind);
+  if (!(tau > 0.f)) {   // at maturity: g(x), 0, dg/dx
+    double s = 0.0;
+    for (int d = 0; d < a.gcols; ++d) s += squares ? (double)xp[d] * (double)xp[d] : (double)xp[d];
+    double g, gp;
+    mc_payoff(a.g_kind, s, (double)a.gcols, (double)a.strike, (double)a.g_alpha, g, gp);
+    if (c == 0) {
+      value[p] = (float)g;
+      if (stderr_) stderr_[p] = 0.f;
+    } else {
+      delta[(size_t)p * a.D + c - 1] = c - 1 < a.gcols ? (float)(gp * (squares ? 2.0 * (double)xp[c - 1] : 1.0)) : 0.f;
+    }
+    return;
+  }
+  const double disc = exp(-(double)a.phi_r * (double)tau), n = (double)a.mc;
+  const double* q = a.part + (size_t)p * a.nch * a.W;
+  if (c == 0) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int h = 0; h < a.nch; ++h) {
+      s1 += q[(size_t)h * a.W];
+      s2 += q[(size_t)h * a.W + 1];
+    }
+    value[p] = (float)(disc * (s1 / n));
+    if (stderr_) {
+      double var = a.mc > 1 ? (s2 - s1 * s1 / n) / (n - 1.0) : 0.0;
+      if (!(var > 0.0)) var = 0.0;
+      stderr_[p] = (float)(disc * sqrt(var / n));
+    }
+  } else {
+    double s1 = 0.0;
+    for (int h = 0; h < a.nch; ++h) s1 += q[(size_t)h * a.W + 1 + c];
+    delta[(size_t)p * a.D + c - 1] = (float)(disc * (s1 / n));
+  }
+}
+
+}  // namespace dbsde
+
+using namespace dbsde;
+
+namespace {
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const float* L, const float* t,
+                              const float* x, int P, int n_steps, long long mc, unsigned long long seed,
+                              unsigned long long offset, float* value, float* stderr_, float* delta, void* stream) {
+  auto bad = [](const std::string& m) { return fail(nullptr, DBSDE_EINVAL, "dbsde_mc_value: " + m); };
+  if (!prob || !t || !x || !value) return bad("prob, t, x and value must not be NULL");
+  if (P < 1 || D < 1 || n_steps < 1 || mc < 1) return bad("P, D, n_steps and mc must be >= 1");
+  if (mc > (1LL << 32)) return bad("mc must be <= 2^32 (the sample index is a 32-bit counter word)");
+  if (D > MC_DMAX) return bad("D must be <= 4096");
+  if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON) return bad("unknown problem kind");
+  if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_CALL) return bad("unknown terminal condition g_kind");
+  if (prob->phi_zz != 0.f)
+    return bad("phi_zz != 0 is not a linear problem (no Feynman-Kac expectation); the HJB comparator is dbsde_hjb_mc");
+  const bool heston = prob->kind == DBSDE_PROB_HESTON;
+  if (heston && (D & 1)) return bad("the Heston state [S_1..S_k, v_1..v_k] needs an even D");
+  if (heston && L) return bad("L applies to DIAG problems only");
+  if (heston && delta)
+    return bad("no pathwise delta for Heston (the S and v tangents couple); bump and reprice on the same draws");
+  if (L && D > MC_NBMAX) return bad("L needs D <= 128");
+
+  McArgs a{};
+  a.D = D;
+  a.nd = heston ? D / 2 : D;
+  a.P = P;
+  const int tiles = (P + MC_PT - 1) / MC_PT;
+  a.Ppad = tiles * MC_PT;
+  a.n_steps = n_steps;
+  a.nj = a.nd > MC_THREADS ? (a.nd + MC_THREADS - 1) / MC_THREADS : 1;
+  a.S = a.nj > 1 ? 1 : (MC_THREADS / a.nd < MC_SMAX ? MC_THREADS / a.nd : MC_SMAX);
+  const long long per0 = (mc + MC_CHUNKS - 1) / MC_CHUNKS;
+  a.per = (per0 + a.S - 1) / a.S * a.S;
+  a.nch = (int)((mc + a.per - 1) / a.per);
+  a.W = 2 + (delta ? D : 0);
+  a.g_kind = prob->g_kind;
+  a.gcols = prob->g_cols > 0 && prob->g_cols < D ? prob->g_cols : D;
+  a.strike = prob->strike;
+  a.g_alpha = prob->g_alpha;
+  a.phi_r = prob->phi_r;
+  a.T = T;
+  volatile float fold = prob->phi_r * prob->phi_c;   // rounded on its own, then added
+  a.mu = heston ? prob->mu_a : prob->mu_a + fold;
+  a.sig_a = prob->sig_a;
+  a.sig_b = prob->sig_b;
+  a.kappa = prob->h_kappa;
+  a.theta = prob->h_theta;
+  a.hsig = prob->h_sigma;
+  a.rho = prob->h_rho;
+  a.mc = mc;
+  a.seed = seed;
+  a.offset = offset;
+  a.t = t;
+  a.x = x;
+  a.L = L;
+
+  hipStream_t st = (hipStream_t)stream;
+  const size_t b_part = up256((size_t)P * a.nch * a.W * sizeof(double));
+  const size_t b_dtab = up256((size_t)n_steps * a.Ppad * sizeof(float));
+  const size_t b_sq = up256((size_t)a.Ppad * sizeof(float));
+  const size_t b_lp = L ? up256((size_t)MC_LPACK * sizeof(float)) : 0;
+  char* buf = nullptr;
+  if (hipMallocAsync((void**)&buf, b_part + b_dtab + b_sq + b_lp, st) != hipSuccess)
+    return fail(nullptr, DBSDE_ENOMEM, "dbsde_mc_value: hipMallocAsync failed");
+  a.part = (double*)buf;
+  a.dtab = (float*)(buf + b_part);
+  a.sqdt = (float*)(buf + b_part + b_dtab);
+  a.Lp = L ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
+
+  mc_grid_kernel<<<(a.Ppad + 255) / 256, 256, 0, st>>>(a);
+  const dim3 grid(tiles, a.nch);
+  if (heston)
+    mc_kernel<MC_HESTON, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (L && delta)
+    mc_kernel<MC_CORR, true><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (L)
+    mc_kernel<MC_CORR, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (delta)
+    mc_kernel<MC_DIAG, true><<<grid, MC_THREADS, 0, st>>>(a);
+  else
+    mc_kernel<MC_DIAG, false><<<grid, MC_THREADS, 0, st>>>(a);
+  mc_final_kernel<<<dim3(P, ((delta ? D : 0) + 256) / 256), 256, 0, st>>>(a, value, stderr_, delta);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(buf, st);
+  if (e != hipSuccess) return fail(nullptr, DBSDE_EHIP, std::string("dbsde_mc_value: ") + hipGetErrorString(e));
+  return DBSDE_OK;
+}

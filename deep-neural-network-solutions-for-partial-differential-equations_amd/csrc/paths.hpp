@@ -17,26 +17,14 @@
 // HIP contracts a*b + c into an FMA by default (-ffp-contract=fast), and its
 // __fmul_rn/__fadd_rn are plain operators whose contract flag comes from the
 // header that defines them, so a pragma at the call site does not stop the
-// fusion.  The path kernels use rn_mul/rn_add/rn_sub below, whose operations
+// fusion.  The path kernels use rn_mul/rn_add/rn_sub of rn.hpp, whose operations
 // carry no contract flag: the reference (torch CPU) rounds each product and
 // sum, and X is bit-exact against it.
 #pragma once
 #include "philox.hpp"
+#include "rn.hpp"
 
 namespace dbsde {
-
-__device__ __forceinline__ float rn_mul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float rn_add(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float rn_sub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
 
 enum PathOut { PATH_ROLLOUT = 0, PATH_FETCH_W = 1, PATH_FETCH_DW = 2 };
 
@@ -714,8 +702,6 @@ __global__ void __launch_bounds__(CP_THREADS) rollout_corr_kernel(RolloutArgs p)
 //   X1    = (X0 + mu dt) + (Sig_i0 + Sig_i1) dW     (einsum sums over j first)
 //   sdw_i = Sig_i0 dW + Sig_i1 dW                   (the Y-tilde term, :641-642)
 // --------------------------------------------------------------------------
-__device__ __forceinline__ float clamp100(float v) { return fminf(fmaxf(v, -100.f), 100.f); }
-
 __global__ void __launch_bounds__(256) rollout_heston_kernel(RolloutArgs p) {
   const int k = p.nb;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;

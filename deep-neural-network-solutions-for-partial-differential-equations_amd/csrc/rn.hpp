@@ -1,0 +1,31 @@
+// rn.hpp -- individually rounded fp32 operations for the Euler path step
+// (shared by the rollout kernels of paths.hpp and the Monte-Carlo comparator
+// of mc.hip).
+//
+// HIP contracts a*b + c into an FMA by default (-ffp-contract=fast), and its
+// __fmul_rn/__fadd_rn are plain operators whose contract flag comes from the
+// header that defines them, so a pragma at the call site does not stop the
+// fusion.  rn_mul/rn_add/rn_sub below carry no contract flag: the reference
+// (torch CPU) rounds each product and sum, and X is bit-exact against it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace dbsde {
+
+__device__ __forceinline__ float rn_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float rn_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float rn_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+// the reference's clamp of the Heston drift and diffusion entries
+__device__ __forceinline__ float clamp100(float v) { return fminf(fmaxf(v, -100.f), 100.f); }
+
+}  // namespace dbsde

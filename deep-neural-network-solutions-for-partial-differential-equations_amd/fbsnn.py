@@ -32,6 +32,7 @@ import torch.distributed as dist
 
 from . import generic, networks
 from .solver import NativeSolver, ProblemSpec
+from .solver import mc_value as _mc_value
 
 OPTIMIZER_NAMES = ("Adam", "SGD", "RMSprop", "AdamW", "Adadelta", "Adagrad", "Adamax", "ASGD", "LBFGS")
 NATIVE_OPTIMIZERS = OPTIMIZER_NAMES
@@ -742,6 +743,35 @@ class FBSNN(ABC):
             W_star = W_star.repeat(bs, 1, 1)
         out = self._run(t_star, W_star, Xi_star)
         return out["X"], out["Y"]
+
+    def _mc_state(self, X):
+        """The [P, state_dim] points mc_value evaluates (Heston appends v0)."""
+        X = torch.as_tensor(np.asarray(X) if not isinstance(X, torch.Tensor) else X,
+                            dtype=torch.float32).to(self.device)
+        return X.reshape(-1, self.state_dim).contiguous()
+
+    def mc_value(self, t, X, mc=2 ** 16, n_steps=None, seed=0, delta=False):
+        """Monte-Carlo comparator for this object's problem at the points
+        (t [P], X [P, D]): the Feynman-Kac expectation E[exp(-phi_r tau) g(X_T)]
+        under the problem's own Euler scheme (solver.mc_value, dbsde_mc_value),
+        with this object's problem_spec(), T, strike and -- for a correlated
+        diagonal problem -- the Cholesky factor its device mode uses.  n_steps
+        defaults to self.N.  Every point sees the same Philox draws.  Returns
+        (value [P, 1], stderr [P, 1], delta [P, D] or None).  Linear problems
+        only: phi_zz != 0 (HJB) raises ValueError (use hjb_mc), and so does a
+        problem running its own coefficient methods (the generic path), whose
+        SDE the kernel does not know."""
+        if not self.native_coefficients:
+            raise ValueError(f"{type(self).__name__} runs its own coefficient methods ({self.generic_reason}); "
+                             "mc_value needs a problem_spec() the native step runs")
+        spec = self.problem_spec()
+        if spec.phi_zz != 0:
+            raise ValueError(f"{type(self).__name__} is not linear (phi_zz != 0): its comparator is hjb_mc")
+        X = self._mc_state(X)
+        t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1).contiguous()
+        L = self._L if (self._L is not None and spec.kind == "diag") else None
+        return _mc_value(spec, t, X, self.T, self.N if n_steps is None else n_steps, mc=mc, seed=seed, L=L,
+                         delta=delta)
 
     # ------------------------------------------------------------------ checkpoints
     def save_model(self, file_name):

@@ -265,6 +265,40 @@ class HestonFBSNN(FBSNN):
             gamma = torch.autograd.grad(delta, S, grad_outputs=torch.ones_like(delta))[0]
         return Y.detach().cpu().numpy(), delta.detach().cpu().numpy(), gamma.detach().cpu().numpy()
 
+    def _mc_state(self, X):
+        """mc_value's points: [S_1..S_k] rows get v0 appended, as predict
+        starts the variance; [S.., v..] rows (2k columns) are taken as given."""
+        k = self.n_assets
+        x = torch.as_tensor(np.asarray(X) if not isinstance(X, torch.Tensor) else X,
+                            dtype=torch.float32).to(self.device)
+        if x.dim() == 2 and x.shape[1] == 2 * k:
+            return x.contiguous()
+        return self._full_state(x.reshape(-1, k))
+
+    def mc_greeks(self, S, v, t, mc=2 ** 16, n_steps=None, seed=0, h=0.01):
+        """Monte-Carlo (price, delta, gamma) at the points of calculate_greeks,
+        with its shapes: numpy ([R, 1], [R, k], [R, k]).  Delta and gamma are the
+        central differences in S of mc_value at S - h, S, S + h, all three
+        evaluated in ONE call and therefore on the same draws, so the differences
+        are deterministic -- the bump-and-reprice of the reference's
+        delta_surface / gamma_surface (numerics/heston_closed_form_ii.py:46-83)
+        on this problem's own process.  For k > 1 all S columns are bumped
+        together, matching calculate_greeks' all-ones cotangent: delta is the
+        directional derivative along (1, .., 1) and gamma its second difference,
+        each repeated over the k columns.  No u clamp is applied (the expectation
+        of a non-negative payoff needs none)."""
+        k = self.n_assets
+        S = torch.as_tensor(np.asarray(S), dtype=torch.float32).to(self.device).reshape(-1, k)
+        v = torch.as_tensor(np.asarray(v), dtype=torch.float32).to(self.device).reshape(-1, k)
+        t = torch.as_tensor(np.asarray(t), dtype=torch.float32).to(self.device).reshape(-1)
+        R = S.shape[0]
+        X = torch.cat([torch.cat([S + b, v], dim=1) for b in (-float(h), 0.0, float(h))], dim=0)
+        val, _, _ = self.mc_value(t.repeat(3), X, mc=mc, n_steps=n_steps, seed=seed)
+        dn, mid, up = (val[i * R:(i + 1) * R].double() for i in range(3))
+        delta = ((up - dn) / (2.0 * h)).float().repeat(1, k)
+        gamma = ((up - 2.0 * mid + dn) / (h * h)).float().repeat(1, k)
+        return mid.float().cpu().numpy(), delta.cpu().numpy(), gamma.cpu().numpy()
+
 
 __all__ = ["CallOption", "CallOption1D", "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN"]

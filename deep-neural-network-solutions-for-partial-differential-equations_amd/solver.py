@@ -371,3 +371,38 @@ def hjb_mc(t, X, T, mc=10 ** 5, seed=0):
     _lib.check(lib.dbsde_hjb_mc(_ptr(t), _ptr(X), P, D, float(T), int(mc), int(seed) & (2 ** 64 - 1), _ptr(u),
                                 ctypes.c_void_p(s)))
     return u
+
+
+def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta=False):
+    """Feynman-Kac Monte-Carlo value of a linear problem (include/dbsde.h
+    dbsde_mc_value): u(t, x) = E[exp(-phi_r tau) g(X_T)] under the problem's own
+    Euler scheme with drift mu_a + phi_r phi_c, on the device-mode rollout's
+    Philox draws -- the same draws for every point (common random numbers).
+    spec: a ProblemSpec with phi_zz == 0 (HJB: hjb_mc); t [P], X [P, D] float32
+    cuda tensors (Heston: D = 2k, [S.., v..]); L: an optional [D, D] lower
+    Cholesky factor (diag problems, D <= 128).  Returns (value [P, 1], stderr
+    [P, 1], delta [P, D] or None); delta is the pathwise estimator (diag only)."""
+    if spec.phi_zz != 0:
+        raise ValueError("mc_value needs a linear problem (phi_zz == 0); the HJB comparator is hjb_mc")
+    lib = _lib.load()
+    X = X.reshape(X.shape[0], -1).contiguous().float()
+    t = t.reshape(-1).contiguous().float()
+    P, D = X.shape
+    if t.numel() != P or X.device.type != "cuda" or t.device != X.device:
+        raise ValueError("t [P] and X [P, D] must be float32 tensors on the same HIP device")
+    Ld = None
+    if L is not None:
+        import numpy as np
+        Ld = torch.as_tensor(np.ascontiguousarray(np.asarray(L.cpu() if isinstance(L, torch.Tensor) else L,
+                                                             dtype=np.float32))).to(X.device)
+        if tuple(Ld.shape) != (D, D):
+            raise ValueError(f"L must be [{D}, {D}]")
+    value = torch.empty((P, 1), device=X.device)
+    err = torch.empty((P, 1), device=X.device)
+    dl = torch.empty((P, D), device=X.device) if delta else None
+    prob = spec.to_c()
+    s = torch.cuda.current_stream(X.device).cuda_stream
+    _lib.check(lib.dbsde_mc_value(ctypes.byref(prob), D, float(T), _ptr(Ld), _ptr(t), _ptr(X), P, int(n_steps),
+                                  int(mc), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _ptr(value),
+                                  _ptr(err), _ptr(dl), ctypes.c_void_p(s)))
+    return value, err, dl

@@ -370,6 +370,59 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
 int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long long mc, unsigned long long seed,
                  float* u, void* hip_stream);
 
+/*
+ * Feynman-Kac Monte-Carlo comparator for every LINEAR problem (the device
+ * counterpart of the reference drivers' Monte-Carlo pricers:
+ * with_corr...py:1283-1325, basket_pricer.py, numerics/multidimensional_mc_pricer.py,
+ * numerics/heston_closed_form_ii.py:6-83 -- but simulating the problem's own SDE).
+ *
+ * With phi_zz == 0, phi = phi_r (Y - phi_c X.Z) and the BSDE the step trains on
+ * is the PDE  u_t + (mu + phi_r phi_c X).Du + 1/2 tr(sigma sigma^T D^2 u) - phi_r u = 0,
+ * u(T, .) = g, solved by
+ *   u(t, x) = E[ exp(-phi_r tau) g(X~_T) | X~_t = x ],  tau = T - t,
+ * X~ following the problem's own Euler scheme with drift coefficient
+ * mu_eff = mu_a + phi_r phi_c (fp32).  (BSB: mu = 0, sigma = 0.4 X, phi =
+ * r (Y - X.Z) gives exp((r + sigma^2) tau) |x|^2 = DBSDE_EXACT_BSB.)  Heston has
+ * phi_c = 0 and runs its own clamped drift and 2x2 blocks, one Brownian motion
+ * per asset driving both S and v, as the training step does.  phi_zz != 0 (HJB)
+ * is DBSDE_EINVAL: use dbsde_hjb_mc.
+ *
+ *   L       device [nb, nb] row-major lower Cholesky factor, NULL = independent
+ *           increments; DIAG only, nb = D <= 128
+ *   t, x    device t [P], x [P, D] (Heston: D = 2k, [S_1..S_k, v_1..v_k])
+ *   value   device [P]:     exp(-phi_r tau_p) mean_k g(X_T)
+ *   stderr_ device [P], nullable: exp(-phi_r tau_p) std_k(g, ddof = 1) / sqrt(mc)
+ *           (0 for mc == 1)
+ *   delta   device [P, D], nullable, DIAG only: the pathwise estimator
+ *           exp(-phi_r tau_p) mean_k dg/dX_d(X_T) J_d, J the tangent of the Euler
+ *           step, J <- (J + (mu_eff J) dt) + (sig_a J) dW_d, J_0 = 1; 1/2 at the
+ *           kink of the call payoffs, 0 in the columns past g_cols.  Heston with
+ *           delta != NULL is DBSDE_EINVAL (its S and v tangents couple): bump
+ *           and reprice on the same draws instead.
+ *
+ * Point p runs the training grid with T replaced by tau_p = fp32(T) - t_p:
+ * t_n = fp32(fp64 cumsum of tau_p / n_steps), dt_n their fp32 differences,
+ * sqrt(dt) = sqrtf(tau_p / n_steps).  The normals of sample k, step n, Brownian
+ * coordinate d are those the device-mode rollout draws for global path k
+ * (Philox counter (d, n / 4, k, offset), key from seed), for EVERY point of the
+ * call: common random numbers, so a surface is smooth in x and differences of
+ * neighbouring points carry no sampling noise of their own.  A point's result
+ * depends neither on P nor on its index in the call.  The state is fp32 and
+ * the step is the training step's, in the reference's operation order;
+ * sum g, sum g^2 and the delta sums are fixed-order fp64 sums: the result is
+ * bitwise repeatable.  g runs over the first g_cols columns as in the step;
+ * u_clamp and q3 are ignored.  A point with tau_p <= 0 returns g(x_p), standard
+ * error 0 and dg/dx_p.
+ *
+ * DBSDE_EINVAL before any HIP call: NULL prob / t / x / value; P, D, n_steps
+ * or mc < 1; mc > 2^32; D > 4096; Heston with an odd D, with L or with delta;
+ * L with D > 128; an unknown kind or g_kind; phi_zz != 0.  Needs no context;
+ * the work is enqueued on hip_stream.
+ */
+int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const float* L, const float* t, const float* x, int P,
+                   int n_steps, long long mc, unsigned long long seed, unsigned long long offset, float* value,
+                   float* stderr_, float* delta, void* hip_stream);
+
 /* Per-kernel timing with HIP events on the context stream (bench/profiling). */
 int dbsde_profile_enable(dbsde_ctx* ctx, int enable);
 int dbsde_profile_count(dbsde_ctx* ctx);
