@@ -27,7 +27,7 @@ EXPORTED = [
     "dbsde_abi_version", "dbsde_create", "dbsde_destroy", "dbsde_last_error", "dbsde_set_stream",
     "dbsde_param_count", "dbsde_param_used_mask", "dbsde_matrix_form", "dbsde_brownian_dim", "dbsde_set_corr", "dbsde_brownian", "dbsde_prefetch",
     "dbsde_prefetch_cancel",
-    "dbsde_loss_grad", "dbsde_net_u", "dbsde_net_u_vjp", "dbsde_net_u_xvjp", "dbsde_optimizer_step", "dbsde_exact", "dbsde_hjb_mc",
+    "dbsde_loss_grad", "dbsde_net_u", "dbsde_net_u_vjp", "dbsde_net_u_xvjp", "dbsde_net_u_jet", "dbsde_pde_residual", "dbsde_optimizer_step", "dbsde_exact", "dbsde_hjb_mc",
     "dbsde_mc_value",
     "dbsde_profile_enable", "dbsde_profile_count", "dbsde_profile_read", "dbsde_profile_reset",
     "dbsde_vec_reduce", "dbsde_vec_axpby", "dbsde_lbfgs_direction", "dbsde_train_step",
@@ -61,6 +61,10 @@ class Batch(ctypes.Structure):
 class Outputs(ctypes.Structure):
     _fields_ = [("loss", ctypes.c_void_p), ("X", ctypes.c_void_p), ("Y", ctypes.c_void_p),
                 ("Z", ctypes.c_void_p)]
+
+
+class PdeTerms(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("u", "u_t", "drift", "diffusion", "phi", "residual", "scale")]
 
 
 class Optim(ctypes.Structure):
@@ -108,6 +112,8 @@ def load():
         "dbsde_net_u": (i, [vp, vp, i, vp, vp, vp, vp]),
         "dbsde_net_u_vjp": (i, [vp, vp, i, vp, vp, vp, vp, vp]),
         "dbsde_net_u_xvjp": (i, [vp, vp, i, vp, vp, vp, vp, vp, vp]),
+        "dbsde_net_u_jet": (i, [vp, vp, i, vp, vp, i, vp, vp, vp]),
+        "dbsde_pde_residual": (i, [vp, vp, i, vp, vp, ctypes.POINTER(PdeTerms)]),
         "dbsde_optimizer_step": (i, [vp, vp, vp, vp, vp, ctypes.POINTER(Optim)]),
         "dbsde_profile_enable": (i, [vp, i]),
         "dbsde_profile_count": (i, [vp]),

@@ -155,6 +155,18 @@ struct dbsde_ctx {
   // only where BtZ itself is read (dbsde_net_u_xvjp's input cotangent)
   PackDesc* d_prepz = nullptr;
   int n_prepz = 0, prepz_blocks = 1;
+  // fused contexts: the fp32 BtIn / Bf copies the jet kernels read (jet.hpp),
+  // packed only by dbsde_net_u_jet / dbsde_pde_residual
+  PackDesc* d_prepj = nullptr;
+  int n_prepj = 0, prepj_blocks = 1;
+  // jet rows per launch and per direction workspace (0: the default; DBSDE_JET_CAP)
+  long long jet_cap = 0;
+  // dbsde_pde_residual workspace: u / Du of the points, one chunk's directions
+  // and its (d1, d2)
+  float *jet_u = nullptr, *jet_du = nullptr, *jet_V = nullptr, *jet_d = nullptr;
+  size_t jet_u_cap = 0, jet_du_cap = 0, jet_V_cap = 0, jet_d_cap = 0;
+  unsigned* jet_img = nullptr;   // the weights as split-bf16 fragments (jet.hip jet_split_kernel)
+  size_t jet_img_cap = 0;
 
   int prep_blocks = 1;   // pack_tagged_kernel grid.x: one element per thread
   PackDesc* d_fin = nullptr;
@@ -281,6 +293,9 @@ struct FusedVariant {
 const FusedVariant& fused_at(int fv);
 int fused_variant(int T, int TD, int K, int act, bool hv, bool x3, bool cs = false);
 int fill_col0(dbsde_ctx* c, float* buf, int ld, long long rows, float v);   // buf[r * ld] = v
+// the fp32 weights the jet kernels read (jet.hip): full = the whole weight prep
+// first (NAIS projection, every pack), else only what a prep already run left out
+int jet_pack_weights(dbsde_ctx* c, const float* params, bool full);
 
 // rows per 64-row phase-kernel workgroup (a multiple of the chain-GEMM tile,
 // 64, and of the column-split workgroup, 16)

@@ -391,17 +391,21 @@ int build_buffers(dbsde_ctx* c) {
   };
 
   // ---- prep descriptors: flat params -> packed weight buffers
-  std::vector<PackDesc> P, PZ;
+  std::vector<PackDesc> P, PZ, PJ;   // PJ: the fp32 copies a fused context skips, for the jet kernels
+  auto keep = [&](const PackDesc& d) {
+    if (images_only) PJ.push_back(d);
+    return d;
+  };
   auto add_x_level = [&](int j, const Lin& w, const Lin* b2) {
     float* dst = c->BtIn + (size_t)c->col[j] * Dp;
-    P.push_back(frag(mk_desc(ptag(w.w), D + 1, dst, Dp, w.out, D + 1, 0, PK_COPY), c->imgX[j], TDp, TW, 0, 0));
+    P.push_back(frag(keep(mk_desc(ptag(w.w), D + 1, dst, Dp, w.out, D + 1, 0, PK_COPY)), c->imgX[j], TDp, TW, 0, 0));
     if (b2) {
       PackDesc d = mk_desc(ptag(w.b), 1, dst + D + 1, Dp, w.out, 1, 0, PK_ADD2);
       d.src2 = ptag(b2->b);
       d.src2_ld = 1;
-      P.push_back(frag(d, c->imgX[j], TDp, TW, 0, D + 1));
+      P.push_back(frag(keep(d), c->imgX[j], TDp, TW, 0, D + 1));
     } else {
-      P.push_back(frag(mk_desc(ptag(w.b), 1, dst + D + 1, Dp, w.out, 1, 0, PK_COPY), c->imgX[j], TDp, TW, 0, D + 1));
+      P.push_back(frag(keep(mk_desc(ptag(w.b), 1, dst + D + 1, Dp, w.out, 1, 0, PK_COPY)), c->imgX[j], TDp, TW, 0, D + 1));
     }
     const PackDesc z = mk_desc(ptag(w.w), D + 1, c->BtZ + c->col[j], c->Stot_x, w.out, D + 1, 1, PK_COPY);
     P.push_back(frag(z, c->imgZ[j], TW, TDp, 0, 0));
@@ -417,6 +421,8 @@ int build_buffers(dbsde_ctx* c) {
       PackDesc d = mk_desc(c->rtr[j], LW, c->Bf[j], c->Wp[j - 1], LW, LW, 0, PK_NEGPROJ);
       d.proj = c->proj_part + (size_t)(j - 1) * nblk;
       d.proj_n = nblk;
+      d.proj_norm = nullptr;
+      keep(d);
       d.proj_norm = c->norms + (j - 1);
       P.push_back(frag(d, c->imgF[j], TW, TW, 0, 0));
       d = mk_desc(c->rtr[j], LW, c->Bb[j], c->Wp[j], LW, LW, 1, PK_NEGPROJ);
@@ -425,8 +431,8 @@ int build_buffers(dbsde_ctx* c) {
       d.proj_norm = nullptr;
       P.push_back(frag(d, c->imgB[j], TW, TW, 0, 0));
     } else {
-      P.push_back(frag(mk_desc(ptag(b.w), b.in, c->Bf[j], c->Wp[j - 1], b.out, b.in, 0, PK_COPY), c->imgF[j], TW,
-                       TW, 0, 0));
+      P.push_back(frag(keep(mk_desc(ptag(b.w), b.in, c->Bf[j], c->Wp[j - 1], b.out, b.in, 0, PK_COPY)), c->imgF[j],
+                       TW, TW, 0, 0));
       P.push_back(frag(mk_desc(ptag(b.w), b.in, c->Bb[j], c->Wp[j], b.out, b.in, 1, PK_COPY), c->imgB[j], TW, TW, 0,
                        0));
       P.push_back(mk_desc(ptag(b.b), 1, c->beta[j], 1, b.out, 1, 0, PK_COPY));
@@ -568,6 +574,12 @@ int build_buffers(dbsde_ctx* c) {
     if ((rc = dalloc_t(c, &c->d_prepz, PZ.size()))) return rc;
     HIPC(c, hipMemcpy(c->d_prepz, PZ.data(), PZ.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
   }
+  c->n_prepj = (int)PJ.size();
+  if (c->n_prepj) {
+    for (const PackDesc& d : PJ) c->prepj_blocks = std::max(c->prepj_blocks, (d.rows * d.cols + 255) / 256);
+    if ((rc = dalloc_t(c, &c->d_prepj, PJ.size()))) return rc;
+    HIPC(c, hipMemcpy(c->d_prepj, PJ.data(), PJ.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
+  }
   if ((rc = dalloc_t(c, &c->d_fin, F.size()))) return rc;
   // descriptors are stored with tagged pointers; the kernel arguments carry the
   // real params/grad bases (pack_kernel_tagged below).
@@ -665,6 +677,7 @@ int dbsde_create(const dbsde_config* cfg, dbsde_ctx** out) {
     else if ((e = hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, cfg->device)) != hipSuccess)
       rc = fail(c, DBSDE_EHIP, hipGetErrorString(e));
     if (const char* ec = getenv("DBSDE_CHUNKS")) c->chunks = std::max(0, atoi(ec));
+    if (const char* ej = getenv("DBSDE_JET_CAP")) c->jet_cap = std::max(16, atoi(ej));
   }
   if (!rc) rc = build_buffers(c);
   if (!rc) {

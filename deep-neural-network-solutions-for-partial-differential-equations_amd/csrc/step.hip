@@ -1067,6 +1067,16 @@ int net_u_vjp_impl(dbsde_ctx* c, const float* params, int R, const float* t, con
 
 }  // namespace
 
+int jet_pack_weights(dbsde_ctx* c, const float* params, bool full) {
+  int rc;
+  if (full && (rc = prep_weights(c, params))) return rc;
+  hipStream_t s = c->stream;
+  if (c->n_prepj)   // fused contexts pack only the fragment images per step
+    RUN(c, s, "pack_weights_jet", 0.0, 0.0,
+        pack_tagged_kernel<<<dim3(c->prepj_blocks, c->n_prepj), 256, 0, s>>>(c->d_prepj, params, nullptr));
+  return DBSDE_OK;
+}
+
 extern "C" {
 
 int dbsde_loss_grad(dbsde_ctx* c, const float* params, const dbsde_batch* b, float* grad,

@@ -361,6 +361,72 @@ class FBSNN(ABC):
         self.solver.net_u(self.params, t, X, u, du)
         return u, du
 
+    def _points(self, t, X):
+        X = torch.as_tensor(X, dtype=torch.float32).to(self.device).detach()
+        if X.dim() == 1:
+            X = X.unsqueeze(-1)
+        X = X.reshape(-1, self.state_dim).contiguous()
+        t = torch.as_tensor(t, dtype=torch.float32).to(self.device).detach().reshape(-1).contiguous()
+        if t.numel() != X.shape[0]:
+            raise ValueError(f"t has {t.numel()} values for {X.shape[0]} points")
+        return t, X
+
+    def theta(self, t, X):
+        """u_t [R, 1] at the points: the first directional derivative of the
+        network along e_t (solver.net_u_jet; net_u itself does not
+        differentiate t).  Also available as u_t(t, X): HestonFBSNN keeps the
+        reference's attribute theta (the variance's long-run mean), which
+        shadows this method on its instances; there u_t is the theta of
+        u = max(net, 0)."""
+        t, X = self._points(t, X)
+        R = X.shape[0]
+        V = torch.zeros((R, 1, self.state_dim + 1), device=self.device)
+        V[:, 0, 0] = 1.0
+        d1 = torch.empty((R, 1), device=self.device)
+        self.solver.net_u_jet(self.params, t, X, V, d1=d1)
+        return d1
+
+    u_t = theta
+
+    def pde_residual(self, t, X):
+        """How well the network satisfies its PDE at the points (t [R], X [R, D]):
+        the terms of u_t + mu . Du + 1/2 tr(sigma sigma^T D^2 u) - phi(x, u, Du)
+        as a dict of [R, 1] tensors -- u, u_t, drift, diffusion, phi, residual
+        (their signed sum) and scale = |u_t| + |drift| + 1/2 sum_j |a_j^T D^2u a_j|
+        + |phi| over the diffusion columns a_j, which the residual is read
+        against.  A problem the native step runs is evaluated by
+        dbsde_pde_residual; one running its own coefficient methods (no
+        problem_spec(), or a mismatching one) evaluates mu_tf / sigma_tf /
+        phi_tf in torch and passes the columns of the diffusion its rollout
+        uses (sigma_tf, times the Cholesky factor when correlated) through
+        solver.net_u_jet; the contraction is the same."""
+        t, X = self._points(t, X)
+        R, D = X.shape
+        if self.native_coefficients:
+            out = {k: torch.empty((R, 1), device=self.device) for k in NativeSolver.PDE_TERMS}
+            self.solver.pde_residual(self.params, t, X, **out)
+            return out
+        with torch.no_grad():
+            u, du = self.net_u(t, X)
+            tc = t.reshape(-1, 1)
+            A = self.sigma_tf(tc, X, u)
+            if self._L is not None:
+                A = torch.matmul(A, torch.as_tensor(self._L, dtype=torch.float32).to(self.device))
+            nd = A.shape[2] + 1
+            V = torch.zeros((R, nd, D + 1), device=self.device)
+            V[:, 0, 0] = 1.0
+            V[:, 1:, 1:] = A.transpose(1, 2)
+            d1 = torch.empty((R, nd), device=self.device)
+            d2 = torch.empty((R, nd), device=self.device)
+            self.solver.net_u_jet(self.params, t, X, V, d1=d1, d2=d2)
+            u_t = d1[:, :1].clone()
+            drift = torch.sum(self.mu_tf(tc, X, u, du) * du, dim=1, keepdim=True)
+            diffusion = 0.5 * torch.sum(d2[:, 1:], dim=1, keepdim=True)
+            phi = self.phi_tf(tc, X, u, du).reshape(R, 1)
+            scale = u_t.abs() + drift.abs() + 0.5 * torch.sum(d2[:, 1:].abs(), dim=1, keepdim=True) + phi.abs()
+            return dict(u=u, u_t=u_t, drift=drift, diffusion=diffusion, phi=phi,
+                        residual=u_t + drift + diffusion - phi, scale=scale)
+
     def _param_grads(self, g):
         """A flat gradient split into named_parameters() order; None for a
         parameter no output depends on (NAIS-Net's input_layers[K]),

@@ -217,6 +217,46 @@ class NativeSolver:
                                              _ptr(grad) if grad is not None else None,
                                              _ptr(xbar) if xbar is not None else None), self.ctx)
 
+    def net_u_jet(self, params, t, X, V, d1=None, d2=None):
+        """First and second directional derivatives of the network in its
+        inputs z = (t, x) (dbsde_net_u_jet): for directions V [R, nd, D+1]
+        (column 0 = the t component), d1 [R, nd] <- grad_z net . v and
+        d2 [R, nd] <- v^T hess_z net v.  Each output is optional (None: not
+        computed); at least one is required.  t is differentiated here."""
+        if d1 is None and d2 is None:
+            raise ValueError("net_u_jet needs d1, d2 or both")
+        R = X.numel() // self.D
+        self._check_tensor(params, "params", self.nparams)
+        self._check_tensor(V, "V")
+        if R < 1 or V.numel() % (R * (self.D + 1)) != 0 or V.numel() == 0:
+            raise ValueError(f"V must hold R * nd rows of D + 1 = {self.D + 1} values")
+        nd = V.numel() // (R * (self.D + 1))
+        for name, v, n in (("t", t, R), ("X", X, R * self.D), ("d1", d1, R * nd), ("d2", d2, R * nd)):
+            self._check_tensor(v, name, n)
+        self._bind_stream()
+        _lib.check(self.lib.dbsde_net_u_jet(self.ctx, _ptr(params), R, _ptr(t), _ptr(X), nd, _ptr(V), _ptr(d1),
+                                            _ptr(d2)), self.ctx)
+
+    PDE_TERMS = ("u", "u_t", "drift", "diffusion", "phi", "residual", "scale")
+
+    def pde_residual(self, params, t, X, u=None, u_t=None, drift=None, diffusion=None, phi=None, residual=None,
+                     scale=None):
+        """The terms of u_t + mu . Du + 1/2 tr(sigma sigma^T D^2 u) - phi = 0 for
+        the context's own problem at the points (t [R], X [R, D])
+        (dbsde_pde_residual); every output is an optional [R] tensor, at least
+        one is required."""
+        outs = dict(u=u, u_t=u_t, drift=drift, diffusion=diffusion, phi=phi, residual=residual, scale=scale)
+        if all(v is None for v in outs.values()):
+            raise ValueError("pde_residual needs at least one output")
+        R = X.numel() // self.D
+        self._check_tensor(params, "params", self.nparams)
+        for name, v, n in (("t", t, R), ("X", X, R * self.D)) + tuple((k, v, R) for k, v in outs.items()):
+            self._check_tensor(v, name, n)
+        terms = _lib.PdeTerms(*[_ptr(outs[k]) for k in self.PDE_TERMS])
+        self._bind_stream()
+        _lib.check(self.lib.dbsde_pde_residual(self.ctx, _ptr(params), R, _ptr(t), _ptr(X), ctypes.byref(terms)),
+                   self.ctx)
+
     def optimizer_step(self, params, grad, m, v, **opt):
         """clip_grad_norm_ + optimizer.step() over the flat parameters; m, v are
         the optimizer's state buffers (see include/dbsde.h DBSDE_OPT_*); opt as

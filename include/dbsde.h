@@ -262,6 +262,38 @@ int dbsde_net_u_xvjp(dbsde_ctx* ctx, const float* params, int R, const float* t,
                      const float* X, const float* ubar, const float* zbar, float* grad,
                      float* xbar);
 
+/* First and second directional derivatives of the network in its inputs z = (t, x):
+ *   d1[r, j] = grad_z net(z_r) . v_rj,   d2[r, j] = v_rj^T hess_z net(z_r) v_rj
+ * V device [R, nd, D+1] (column 0 = the t component), d1 / d2 device [R, nd], each nullable
+ * (both NULL: EINVAL).  u_clamp contexts (Heston): the jets of u = max(net, 0), i.e. 0 on the
+ * rows dbsde_net_u masks.  Bitwise repeatable.  t is differentiated here (direction e_t gives
+ * theta = u_t, which dbsde_net_u / dbsde_net_u_xvjp do not).  Forward (Taylor-mode)
+ * propagation in split-bf16 matrix products with fp32 accumulation; nothing is stored per
+ * (point, direction) row, and rows are launched DBSDE_JET_CAP (default 65536, read at
+ * dbsde_create) at a time.  Hidden widths above 256 are not supported (EINVAL). */
+int dbsde_net_u_jet(dbsde_ctx* ctx, const float* params, int R, const float* t, const float* X,
+                    int nd, const float* V, float* d1, float* d2);
+
+/* The terms of the PDE the context's problem solves,
+ *   u_t + mu . Du + 1/2 tr(sigma sigma^T D^2 u) - phi(x, u, Du) = 0,
+ * at R points: device [R] each, each nullable (all NULL: EINVAL).
+ *   u, u_t     the network value (dbsde_net_u) and its t derivative (jet direction e_t)
+ *   drift      mu . Du: DIAG mu_a X . Du; Heston its clamped drift
+ *   diffusion  1/2 sum_j a_j^T D^2u a_j over the columns a_j of the diffusion matrix: DIAG
+ *              diag(sig_a X + sig_b) . L (L: dbsde_set_corr, else I); Heston Sigma_i . (1, 1)^T
+ *              per asset in its (S_i, v_i) plane, with the rollout's sqrt(max(v, 1e-8)) and
+ *              +-100 clamps
+ *   phi        phi_r (u - phi_c X . Du) + phi_zz |Du|^2   (q3 is ignored)
+ *   residual   u_t + drift + diffusion - phi
+ *   scale      |u_t| + |drift| + 1/2 sum_j |a_j^T D^2u a_j| + |phi|: what the residual is
+ *              read against, so that cancellation in the trace does not hide it
+ * Points are processed in chunks of at most DBSDE_JET_CAP (point, direction) rows. */
+typedef struct dbsde_pde_terms {
+  float *u, *u_t, *drift, *diffusion, *phi, *residual, *scale;
+} dbsde_pde_terms;
+int dbsde_pde_residual(dbsde_ctx* ctx, const float* params, int R, const float* t, const float* X,
+                       const dbsde_pde_terms* out);
+
 /* optimizers (nd_BSPDE_case.py:331-350), torch.optim single-tensor formula order */
 #define DBSDE_OPT_ADAM 0
 #define DBSDE_OPT_ADAMW 1
