@@ -30,6 +30,10 @@ using namespace dbsde;
 inline int pad16(int x) { return (x + 15) / 16 * 16; }
 inline int padw(int x) { return x <= 128 ? pad16(x) : (x + 127) / 128 * 128; }
 inline int nt_for(int w) { return w <= 128 ? w / 16 : 8; }
+// the state-dimension cap: Dp = pad16(D + 2) <= DP_MAX, D <= 1022
+constexpr int DP_MAX = 1024;
+// spare zero rows of BtZ behind Dp for the wide Z GEMM's ragged last column tile
+constexpr int ZG_PAD = 128;
 
 struct Lin {
   long long w = -1, b = -1;

@@ -221,6 +221,81 @@ __global__ void __launch_bounds__(256) cotan_kernel(CotanParams p, double* loss_
   }
   if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
 }
+
+// Wide contexts (Dp > 128): the Z GEMM runs over column tiles, so no epilogue
+// holds a whole Z row.  This kernel does for such a row what the EPI_COTAN
+// epilogue does inside the GEMM: the u-clamp mask on Z, the residual row sums,
+// the residual (interior rows) or terminal mismatch, zbar, rres and lossrow;
+// ubar_kernel follows as in the narrow chain.  One 16-lane group per row:
+// lane l visits columns l, l + 16, ... in ascending order and the 16 partial
+// sums meet in red16's xor butterfly, so the order of every sum is fixed.
+// grid Rp / 16; rows in [R, Rp) write zeros.
+struct ZRowArgs {
+  CotanParams p;        // rowsum / ext unused
+  const float* umask;   // [Rp] u-clamp gradient mask or null
+  float* zfull;         // [Rp, Dp] Z as the GEMM stored it; masked in place
+  float* zbar;          // [Rp, Dp]
+  float* rres;          // [Rp]
+  float* lossrow;       // [Rp]
+};
+__global__ void __launch_bounds__(256) zrow_cotan_kernel(ZRowArgs a) {
+  const CotanParams& p = a.p;
+  const int sub = threadIdx.x & 15;
+  const int r = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (r >= p.Rp) return;
+  RowCotan c{};
+  c.valid = r < p.R;
+  c.n = c.valid ? r % p.N1 : 0;
+  c.term = c.n == p.N1 - 1;
+  c.mask = a.umask ? a.umask[r] : 1.f;
+  const size_t ro = (size_t)r * p.Dp;
+  const float* xr = p.xin + ro;
+  const float* sr = p.sdw + ro;
+  float* zr = a.zfull + ro;
+  float s_zs = 0.f, s_xz = 0.f, s_zz = 0.f, s_x = 0.f, s_xx = 0.f, z1 = 0.f;
+  for (int col = sub; col < p.Dp; col += 16) {
+    const float z = zr[col] * c.mask;
+    if (a.umask) zr[col] = z;
+    if (col >= 1 && col <= p.D) {
+      const float xv = xr[col];
+      s_zs += z * sr[col];
+      s_xz += xv * z;
+      s_zz += z * z;
+      if (col <= p.gcols) {
+        s_x += xv;
+        s_xx += xv * xv;
+      }
+      if (col == 1) z1 = z;
+    }
+  }
+  const floatx4 rs0 = {red16(s_zs), red16(s_xz), red16(s_zz), red16(s_x)};
+  const floatx4 rs1 = {red16(s_xx), red16(z1), c.mask, 0.f};
+  if (c.valid) {
+    const float y = p.u[r];
+    if (!c.term) {
+      c.dt = xr[p.Dp] - xr[0];
+      c.q3s = p.q3S ? p.q3S[c.n] : 0.f;
+      c.res = step_residual(p, rs0, rs1, y, p.u[r + 1], c.dt, c.q3s);
+      c.coefY = -2.f * c.res;
+    } else {
+      c.res = y - terminal_g(p.g_kind, rs0[3], rs1[0], p.gcols, p.strike, p.g_alpha, c.gsc);
+      c.gA = p.g_kind == 0 ? 2.f : (p.g_kind == 3 ? c.gsc : 0.f);
+      c.gB = (p.g_kind == 0 || p.g_kind == 3) ? 0.f : c.gsc;
+    }
+  }
+  float tz = 0.f;
+  float* zb = a.zbar + ro;
+  for (int col = sub; col < p.Dp; col += 16) {
+    float v = 0.f;
+    if (c.valid && col >= 1 && col <= p.D) v = col_zbar(p, c, col, xr[col], zr[col], sr[col], tz);
+    zb[col] = v;
+  }
+  tz = red16(tz);
+  if (sub == 0) {
+    a.rres[r] = c.valid ? c.res : 0.f;
+    a.lossrow[r] = c.valid ? c.res * c.res + tz : 0.f;
+  }
+}
 #endif
 
 }  // namespace dbsde

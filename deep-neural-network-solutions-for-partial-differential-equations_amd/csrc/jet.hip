@@ -314,7 +314,13 @@ template <int TWMAX>
 int launch_tw(const JetArgs& a, int point, hipStream_t s) {
   const unsigned grid = (unsigned)((a.nrows + 16 * JET_NT - 1) / (16 * JET_NT));
   const size_t lds = (size_t)JET_NT * 16 * ((a.Dp + 4) + (point ? 1 : 2) * a.ldw) * sizeof(float);
-  if (lds > 64 * 1024) return -1;
+  // wide contexts stage more than the default 64 KB (Dp = 1024, width 256:
+  // 97 KB); a CU has 160 KB
+  if (lds > 160 * 1024) return -2;
+  if (lds > 64 * 1024) {
+    const void* f = point ? (const void*)jet_kernel<TWMAX, JET_NT, true> : (const void*)jet_kernel<TWMAX, JET_NT, false>;
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+  }
   if (point)
     jet_kernel<TWMAX, JET_NT, true><<<grid, 64, lds, s>>>(a);
   else
@@ -570,6 +576,7 @@ int jet_points(dbsde_ctx* c, const float* params, int R, const float* t, const f
   int ok = 0;
   RUN(c, s, "jet_points", (double)R * jet_flops_row(c, 1),
       4.0 * R * (c->D + 1.0 + 2.0 * c->Stot) + jet_weight_bytes(c), ok = jet_launch(a, 1, s));
+  if (ok == -2) return fail(c, DBSDE_EINVAL, "net_u_jet: the input and state rows exceed the CU's 160 KB of LDS");
   if (ok) return fail(c, DBSDE_EINVAL, "net_u_jet: hidden widths above 256 are not supported");
   return DBSDE_OK;
 }
@@ -588,6 +595,7 @@ int jet_rows(dbsde_ctx* c, long long n, long long g0, long long p0, int nd, cons
   int ok = 0;
   RUN(c, s, "net_u_jet", (double)n * jet_flops_row(c, 2),
       4.0 * n * (c->D + 3.0) + jet_weight_bytes(c), ok = jet_launch(a, 0, s));
+  if (ok == -2) return fail(c, DBSDE_EINVAL, "net_u_jet: the input and state rows exceed the CU's 160 KB of LDS");
   if (ok) return fail(c, DBSDE_EINVAL, "net_u_jet: hidden widths above 256 are not supported");
   return DBSDE_OK;
 }

@@ -131,6 +131,7 @@ enum Epi {
   EPI_TAN,        // adot = acc + (in0?in0:0); hdot = act'(in2)*adot + rho*in1 ; last: out2 = alpha_K
   EPI_REV,        // p = acc + rho*(in0 ? in0 : ubar*vec0) ; out0=p ; out1 = p*act'(in1) + in2*in3*act''(in1)
   EPI_STORE,      // out0 = acc (net_u Z / plain)
+  EPI_STORE_N,    // out0 = acc for the columns below lvl0_cols (wide Z GEMM: the last column tile may be ragged)
 };
 
 struct ChainArgs {
@@ -147,7 +148,7 @@ struct ChainArgs {
   const float* ubar;
   float rho;
   int act;
-  int lvl0_cols;  // EPI_FWD0 / EPI_TAN0: number of padded level-0 columns
+  int lvl0_cols;  // EPI_FWD0 / EPI_TAN0: number of padded level-0 columns; EPI_STORE_N: output columns
   int last;       // EPI_FWD / EPI_TAN: j == K
   // --- EPI_COTAN
   int R, N1, D;
@@ -353,6 +354,8 @@ __global__ void __launch_bounds__(256) chain_gemm_kernel(ChainArgs p) {
         const float v = acc[t][j];
         if constexpr (EPI == EPI_STORE) {
           p.out[0][row * p.ldo[0] + c] = v;
+        } else if constexpr (EPI == EPI_STORE_N) {
+          if (c < p.lvl0_cols) p.out[0][row * p.ldo[0] + c] = v;
         } else if constexpr (EPI == EPI_FWD0) {
           p.out[0][row * p.ldo[0] + c] = v;
           if (c < p.lvl0_cols) p.out[1][row * p.ldo[1] + c] = act_f(p.act, v);

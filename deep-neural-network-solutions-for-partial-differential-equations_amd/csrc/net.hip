@@ -228,7 +228,7 @@ int build_net(dbsde_ctx* c) {
   }
   // padded geometry
   c->Dp = pad16(c->D + 2);
-  if (c->Dp > 128) return fail(c, DBSDE_EINVAL, "D > 126 is not supported by this build (Z epilogue tile)");
+  if (c->Dp > DP_MAX) return fail(c, DBSDE_EINVAL, "D > 1022 is not supported (Dp = pad16(D + 2) must be <= 1024)");
   c->Wp.resize(c->K + 1);
   c->col.resize(c->K + 1);
   c->Stot = 0;
@@ -307,7 +307,7 @@ int build_buffers(dbsde_ctx* c) {
   const int K = c->K, D = c->D, Dp = c->Dp;
   int rc;
   if ((rc = dalloc_t(c, &c->BtIn, (size_t)c->Stot_x * Dp))) return rc;
-  if ((rc = dalloc_t(c, &c->BtZ, (size_t)Dp * c->Stot_x))) return rc;
+  if ((rc = dalloc_t(c, &c->BtZ, (size_t)(Dp + (Dp > 128 ? ZG_PAD : 0)) * c->Stot_x))) return rc;
   if ((rc = dalloc_t(c, &c->wout, (size_t)c->Wp[K]))) return rc;
   if ((rc = dalloc_t(c, &c->bout, 16))) return rc;
   c->Bf.assign(K + 1, nullptr);

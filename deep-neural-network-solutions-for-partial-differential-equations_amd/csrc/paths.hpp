@@ -384,6 +384,9 @@ __global__ void __launch_bounds__(256) rollout_draw_kernel(RolloutArgs p) {
 
 constexpr int RC_THREADS = 64;
 constexpr int RC_AHEAD = 8;   // increments loaded ahead of the chain
+// HOST_T: the caller's time grid p.t instead of the device grid (the wide
+// correlated rollout below runs its Euler chains through this kernel too)
+template <bool HOST_T = false>
 __global__ void __launch_bounds__(RC_THREADS) rollout_chain_kernel(RolloutArgs p) {
   const int C = p.ldx >> 2;
   const int gid = blockIdx.x * RC_THREADS + threadIdx.x;
@@ -401,6 +404,7 @@ __global__ void __launch_bounds__(RC_THREADS) rollout_chain_kernel(RolloutArgs p
   const double dt64 = (double)p.T / (double)p.N;
   double tacc = 0.0;
   float t0 = 0.0f;
+  if constexpr (HOST_T) t0 = p.t[(size_t)m * N1];
   const size_t r0 = (size_t)m * N1;
   for (int n0 = 0; n0 < p.N; n0 += RC_AHEAD) {
     floatx4 dw[RC_AHEAD];
@@ -412,7 +416,8 @@ __global__ void __launch_bounds__(RC_THREADS) rollout_chain_kernel(RolloutArgs p
       const int n = n0 + i;
       if (n >= p.N) break;
       tacc += dt64;
-      const float t1 = (float)tacc;
+      float t1 = (float)tacc;
+      if constexpr (HOST_T) t1 = p.t[(size_t)m * N1 + n + 1];
       const float dt = rn_sub(t1, t0);
       floatx4 xo, so;
 #pragma unroll
@@ -689,6 +694,142 @@ __global__ void __launch_bounds__(CP_THREADS) rollout_corr_kernel(RolloutArgs p)
     case 5: corr_wave<NBLK, corr_block_of_wave<NBLK>(5), -1>(p, xs, stg); break;
     case 6: corr_wave<NBLK, corr_block_of_wave<NBLK>(6), -1>(p, xs, stg); break;
     default: corr_wave<NBLK, corr_block_of_wave<NBLK>(7), -1>(p, xs, stg); break;
+  }
+}
+
+// --------------------------------------------------------------------------
+// Cholesky-correlated device mode for 128 < nb <= 1022.  L no longer fits a
+// workgroup's registers and a step's rows no longer fit its LDS, so the
+// correlation product leaves the Euler chain: dW = L (sqrt(dt) z) does not
+// depend on X, hence every (path, step) pair is one column of a plain
+// triangular GEMM, and the chain runs afterwards, as in the two-pass diagonal
+// rollout.
+//   pass 1 (rollout_corrw_kernel): workgroup = CW_PATHS = 16 paths x one
+//     4-step Philox block = 64 columns (4 MFMA column tiles; column 4 p + k =
+//     path p, step 4 sb + k), 8 waves; wave w owns the output blocks
+//     o = w, w + 8, ... (16 dims each; interleaved, so the triangle's work is
+//     spread evenly), at most 8, all four column tiles of each in
+//     accumulators.  The K loop runs over 16-dim chunks kc = 0 .. nblk - 1: the
+//     uncorrelated sqrt(dt) z of chunk kc + 1 (16 paths x 16 dims = 256 Philox
+//     calls, the key of the uncorrelated rollout: seed, offset, global path,
+//     step block, coordinate) are drawn into one LDS buffer while chunk kc is
+//     multiplied out of the other; block o takes part while kc <= o (the
+//     lower triangle).  The 16 x 16 block of L is streamed from the device
+//     copy L^T (coalesced over the 16 dims of a block, L2-resident: 4 MB at
+//     most) and serves the workgroup's 64 columns.
+//     Summation order of dW[d]: chunks kc ascending; inside a chunk the four
+//     v_mfma_f32_16x16x4_f32 i = 0..3 in order, MFMA i summing k = 16 kc + 4 q
+//     + i over q = 0..3 in the matrix core's fixed order.  fp32 inputs.
+//     The increments go to the sdw rows (column 1 + d), or to the fetch
+//     output.
+//   pass 2: rollout_chain_kernel, the diagonal rollout's Euler chains over
+//     the increments in the sdw rows (whole float4 rows of xin / sdw), or, for
+//     the fetch, corrw_fetch_kernel (t and the fp64 cumulative sums).
+// --------------------------------------------------------------------------
+constexpr int CW_PATHS = 16;
+constexpr int CW_THREADS = 512;
+constexpr int CW_OB = 8;        // output blocks per wave: 8 waves x 8 x 16 = 1024 dims
+constexpr int CW_LS = 20;       // LDS row stride of a 16-dim chunk (16 + 4 pad)
+
+// sqrt(dt) z of dims [16 kc, 16 kc + 16) of the 16 paths, steps 4 sb .. 4 sb + 3:
+// zs[column 4 p + k][dim in chunk]
+__device__ __forceinline__ void corrw_draw(const RolloutArgs& p, int m0, int sb, int kc, float sqdt, float* zs) {
+  if (threadIdx.x >= CW_PATHS * 16) return;
+  const int pp = threadIdx.x & (CW_PATHS - 1), dl = threadIdx.x >> 4;
+  const int d = 16 * kc + dl, m = m0 + pp;
+  float z[4] = {0.f, 0.f, 0.f, 0.f};
+  if (d < p.nb && m < p.M) philox_normal4(p.seed, p.offset, (uint32_t)(p.path0 + m), (uint32_t)sb, (uint32_t)d, z);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) zs[(4 * pp + k) * CW_LS + dl] = (d < p.nb && m < p.M) ? sqdt * z[k] : 0.f;
+}
+
+__global__ void __launch_bounds__(CW_THREADS) rollout_corrw_kernel(RolloutArgs p) {
+  __shared__ __attribute__((aligned(16))) float zs[2][4 * CW_PATHS * CW_LS];
+  const int lane = threadIdx.x & 63, cl = lane & 15, q = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m0 = blockIdx.x * CW_PATHS, sb = blockIdx.y;
+  const int nb = p.nb, nblk = (nb + 15) / 16;
+  const float sqdt = sqrtf(p.T / (float)p.N);
+  cpf4 acc[CW_OB][4];
+#pragma unroll
+  for (int b = 0; b < CW_OB; ++b)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[b][t] = cpf4{0.f, 0.f, 0.f, 0.f};
+  corrw_draw(p, m0, sb, 0, sqdt, zs[0]);
+  __syncthreads();
+  for (int kc = 0; kc < nblk; ++kc) {
+    if (kc + 1 < nblk) corrw_draw(p, m0, sb, kc + 1, sqdt, zs[(kc + 1) & 1]);
+    const float* zb = zs[kc & 1];
+    // B operand: column 16 t + cl, dims 16 kc + 4 q + i (MFMA i takes component i)
+    cpf4 bz[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bz[t] = *(const cpf4*)(zb + (16 * t + cl) * CW_LS + 4 * q);
+#pragma unroll
+    for (int b = 0; b < CW_OB; ++b) {
+      const int o = wave + 8 * b;
+      if (o < nblk && kc <= o) {   // wave-uniform
+        // A operand: L[16 o + cl][16 kc + 4 q + i] = Lt[k][d] (zero above the diagonal)
+        const int d = 16 * o + cl;
+        float la[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int k = 16 * kc + 4 * q + i;
+          la[i] = (d < nb && k < nb) ? p.Lt[(size_t)k * nb + d] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) acc[b][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(la[i], bz[t][i], acc[b][t], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // accumulator (b, t), lane (cl, q), component r: dim 16 o + 4 q + r of column 16 t + cl
+  const int N1 = p.N + 1;
+#pragma unroll
+  for (int b = 0; b < CW_OB; ++b) {
+    const int o = wave + 8 * b;
+    if (o >= nblk) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int colw = 16 * t + cl, m = m0 + (colw >> 2), n = 4 * sb + (colw & 3);
+      if (m >= p.M || n >= p.N) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int d = 16 * o + 4 * q + r;
+        if (d >= nb) continue;
+        const float dw = acc[b][t][r];
+        if (p.out == PATH_ROLLOUT)
+          p.sdw[((size_t)m * N1 + n) * p.ldx + 1 + d] = dw;
+        else if (p.out == PATH_FETCH_DW)
+          p.W_out[((size_t)m * p.N + n) * nb + d] = dw;
+        else
+          p.W_out[((size_t)m * N1 + n + 1) * nb + d] = dw;
+      }
+    }
+  }
+}
+
+// the fetch outputs of the wide correlated kernel: t [M, N+1], and for
+// PATH_FETCH_W the increments left in W_out[m, n + 1] summed into W = fp32(fp64
+// cumulative sum) (FetchAcc's values).  Thread per (path, coordinate).
+__global__ void __launch_bounds__(256) corrw_fetch_kernel(RolloutArgs p) {
+  const long long gid = blockIdx.x * 256LL + threadIdx.x;
+  if (gid >= (long long)p.M * p.nb) return;
+  const int m = (int)(gid / p.nb), d = (int)(gid - (long long)m * p.nb);
+  const int N1 = p.N + 1;
+  const double dt64 = (double)p.T / (double)p.N;
+  double tacc = 0.0, wsum = 0.0;
+  if (d == 0) p.t_out[(size_t)m * N1] = p.t ? p.t[(size_t)m * N1] : 0.f;
+  if (p.out == PATH_FETCH_W) p.W_out[((size_t)m * N1) * p.nb + d] = 0.f;
+  for (int n = 1; n <= p.N; ++n) {
+    tacc += dt64;
+    if (d == 0) p.t_out[(size_t)m * N1 + n] = p.t ? p.t[(size_t)m * N1 + n] : (float)tacc;
+    if (p.out == PATH_FETCH_W) {
+      float* w = p.W_out + ((size_t)m * N1 + n) * p.nb + d;
+      wsum += (double)*w;
+      *w = (float)wsum;
+    }
   }
 }
 

@@ -2,6 +2,8 @@
 // (paths.hpp), the scheduler of the two path buffers and of the rollouts
 // prefetched into them, and the C ABI that drives it (dbsde_prefetch*,
 // dbsde_set_corr, dbsde_brownian).
+// Correlated device mode: rollout_corr_kernel up to nb = 128 (L in registers),
+// above it the increment GEMM rollout_corrw_kernel followed by the Euler chains.
 #include <hip/hip_runtime.h>
 
 // a prefetched rollout runs on the next chunked step's second stream
@@ -33,6 +35,11 @@ int validate_batch(dbsde_ctx* c, const dbsde_batch* b) {
   if (b->xi_rows != 1 && b->xi_rows != b->M) return fail(c, DBSDE_EINVAL, "Xi must have 1 or M rows");
   if (b->W && !b->t) return fail(c, DBSDE_EINVAL, "t is required with W");
   if (b->path0 < 0 || b->path0 + b->M > (1LL << 32)) return fail(c, DBSDE_EINVAL, "path0 out of range");
+  // the path kernels count (path, 16-byte column group) pairs in an int, and a
+  // row buffer of Rp x max(Dp, Stot) floats must be addressable by the launch grids
+  if ((long long)b->M * c->Dp > 0x7fffffffLL) return fail(c, DBSDE_EINVAL, "M * Dp too large");
+  if ((long long)pad_rows(b->M * (b->N + 1)) * std::max(c->Dp, c->Stot) > (1LL << 38))
+    return fail(c, DBSDE_EINVAL, "M*(N+1) rows of this width cannot be indexed");
   return DBSDE_OK;
 }
 
@@ -95,6 +102,25 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
   if (c->heston) {
     const int nthr = ra.M * ra.nb;
     RUN(c, s, name, 0.0, bytes, rollout_heston_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
+  } else if (c->Lt && !ra.W && ra.nb > CP_NBMAX) {
+    // wide correlated device mode (paths.hpp): the triangular GEMM dW = L (sqrt(dt) z)
+    // over (path group, step block), then the Euler chains or the fetch sums
+    if (ra.ldx % 4 != 0 || ra.nb > CW_OB * 8 * 16 || ra.nb != ra.D)
+      return fail(c, DBSDE_EINVAL, "internal: wide correlated rollout geometry");
+    const dim3 g((ra.M + CW_PATHS - 1) / CW_PATHS, (ra.N + 3) / 4);
+    const double fl = 2.0 * steps * ra.nb * ra.nb / 2;
+    RUN(c, s, "corr_increments", fl, 4.0 * steps * ra.nb, rollout_corrw_kernel<<<g, CW_THREADS, 0, s>>>(ra));
+    if (ra.out == PATH_ROLLOUT) {
+      const int chains = ra.M * (ra.ldx / 4);
+      const unsigned gb = (unsigned)((chains + RC_THREADS - 1) / RC_THREADS);
+      if (ra.t)
+        RUN(c, s, name, 0.0, bytes + 4.0 * steps * ra.D, rollout_chain_kernel<true><<<gb, RC_THREADS, 0, s>>>(ra));
+      else
+        RUN(c, s, name, 0.0, bytes + 4.0 * steps * ra.D, rollout_chain_kernel<false><<<gb, RC_THREADS, 0, s>>>(ra));
+    } else {
+      const long long nthr = (long long)ra.M * ra.nb;
+      RUN(c, s, name, 0.0, bytes, corrw_fetch_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, s>>>(ra));
+    }
   } else if (c->Lt && !ra.W) {
     if (ra.ldx > cp_srow((ra.nb + 15) / 16) || ra.ldx % 4 != 0)
       return fail(c, DBSDE_EINVAL, "internal: correlated rollout row staging");
@@ -106,7 +132,7 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
     const int chains = ra.M * (ra.ldx / 4);
     RUN(c, s, name, 0.0, bytes,
         rollout_draw_kernel<<<(unsigned)((draws + 255) / 256), 256, 0, s>>>(ra);
-        rollout_chain_kernel<<<(unsigned)((chains + RC_THREADS - 1) / RC_THREADS), RC_THREADS, 0, s>>>(ra));
+        rollout_chain_kernel<false><<<(unsigned)((chains + RC_THREADS - 1) / RC_THREADS), RC_THREADS, 0, s>>>(ra));
   } else if (DBSDE_RS && ra.out == PATH_ROLLOUT && !ra.W && ra.ldx % 4 == 0) {
     // device-mode increments: draws spread over the time steps (paths.hpp)
     const long long pairs = (long long)ra.M * (ra.ldx / 4);
@@ -300,7 +326,6 @@ int dbsde_set_corr(dbsde_ctx* c, const float* L, int n) {
   }
   if (c->heston) return fail(c, DBSDE_EINVAL, "dbsde_set_corr: correlated increments are for DIAG problems");
   if (n != c->nb) return fail(c, DBSDE_EINVAL, "dbsde_set_corr: L must be [nb, nb], nb = the Brownian dimension");
-  if (n > CP_NBMAX) return fail(c, DBSDE_EINVAL, "dbsde_set_corr: Brownian dimension > 128 is not supported");
   std::vector<float> lt((size_t)n * n, 0.f);
   for (int d = 0; d < n; ++d)
     for (int k = 0; k <= d; ++k) lt[(size_t)k * n + d] = L[(size_t)d * n + k];   // L^T, lower part of L only

@@ -10,6 +10,9 @@
 //   tangent   forward-mode along zbar                         (MFMA fp32)
 //   reverse   K block GEMMs                                   (MFMA fp32)
 //   weight-grad split-K TN GEMMs into slabs, fixed-order slab sums, NAIS adjoint
+// State dimensions above 126 (Dp > 128) run this per-layer sequence with the Z
+// GEMM over column tiles (zgemm_wide) and the residual epilogue as a row kernel
+// behind it (fused.hpp zrow_cotan_kernel); DESIGN 3.6.
 //
 // This unit instantiates the kernels of kernels.hpp, fused.hpp, phase.hpp,
 // chainx3.hpp and tnx3.hpp.
@@ -88,8 +91,12 @@ namespace {
 // ---------------------------------------------------------------------------
 template <int EPI>
 int chain(dbsde_ctx* c, const char* name, ChainArgs& a, int Rp, int NP, int NT, double flops, double bytes) {
-  dim3 grid(Rp / CH_BM, NP / (16 * NT));
-  if (NP % (16 * NT) != 0) return fail(c, DBSDE_EINVAL, "internal: column tiling mismatch");
+  // (EPI_STORE_N: the last column tile may reach past NP; its weight rows are
+  // allocated, zero, and its stores guarded)
+  constexpr bool ragged = EPI == EPI_STORE_N;
+  if (NT < 1) return fail(c, DBSDE_EINVAL, "internal: bad NT");
+  dim3 grid(Rp / CH_BM, (NP + 16 * NT - 1) / (16 * NT));
+  if (!ragged && NP % (16 * NT) != 0) return fail(c, DBSDE_EINVAL, "internal: column tiling mismatch");
   if (a.K % CH_KC != 0) return fail(c, DBSDE_EINVAL, "internal: K not a multiple of 16");
   hipStream_t s = c->stream;
   // split-bf16 form (the weight image must hold this launch's output columns);
@@ -361,6 +368,24 @@ int zgemm_args(dbsde_ctx* c, ChainArgs& a) {
 }
 
 double zgemm_flops(dbsde_ctx* c, int R) { return 2.0 * R * nv_x(c) * c->D; }
+
+// Column tiling of the wide Z GEMM (Dp > 128): ceil(Dp / 128) column tiles of
+// NT <= 8 blocks each, NT the smallest that covers Dp (9 blocks: 2 tiles of 5,
+// 13: 2 of 7, 19: 3 of 7, 64: 8 of 8).  BtZ holds ZG_PAD spare zero rows for
+// the ragged last tile (build_buffers).
+int zgemm_wide_nt(int Dp) {
+  const int nblk = Dp / 16, tiles = (nblk + 7) / 8;
+  return (nblk + tiles - 1) / tiles;
+}
+// Z = Delta . W_in of a wide context into zfull, plain stores
+int zgemm_wide(dbsde_ctx* c, const char* name, int R, int Rp) {
+  ChainArgs a = base_args(c);
+  zgemm_args(c, a);
+  a.lvl0_cols = c->Dp;
+  const int NT = zgemm_wide_nt(c->Dp);
+  if (((c->Dp / 16 + NT - 1) / NT) * NT * 16 > c->Dp + ZG_PAD) return fail(c, DBSDE_EINVAL, "internal: wide Z tiling");
+  return chain<EPI_STORE_N>(c, name, a, Rp, c->Dp, NT, zgemm_flops(c, R), 4.0 * R * (c->Stot_x + (double)c->D));
+}
 
 CotanParams cotan_params(dbsde_ctx* c, int R, int Rp, int N1, bool q3) {
   const dbsde_problem& pr = c->cfg.problem;
@@ -902,7 +927,20 @@ int loss_grad_impl(dbsde_ctx* c, const float* params, const dbsde_batch* b, floa
     if ((rc = forward_and_inputgrad(c, R, Rp))) return rc;
 
     // ---- Z GEMM + residuals / cotangents / loss rows
-    {
+    if (c->Dp > 128) {
+      // wide contexts: the Z GEMM over column tiles, then the row kernel
+      // (fused.hpp zrow_cotan_kernel) for what needs a whole Z row
+      if ((rc = zgemm_wide(c, "gemm_z", R, Rp))) return rc;
+      ZRowArgs za{};
+      za.p = cotan_params(c, R, Rp, N1, q3);
+      za.umask = c->u_clamp ? c->umask : nullptr;
+      za.zfull = c->zfull;
+      za.zbar = c->zbar;
+      za.rres = c->rres;
+      za.lossrow = c->lossrow;
+      RUN(c, s, "z_row_cotangent", 12.0 * R * D, 4.0 * R * (5.0 * c->Dp),
+          zrow_cotan_kernel<<<Rp / 16, 256, 0, s>>>(za));
+    } else {
       ChainArgs a = base_args(c);
       zgemm_args(c, a);
       a.R = R;
@@ -1135,9 +1173,13 @@ int dbsde_net_u(dbsde_ctx* c, const float* params, int R, const float* t, const 
     RUN(c, s, "fused_fwd_inputgrad", 0.0, 0.0, kFused[c->fv].A<<<Rp / WR, 64 * P3_WAVES, 0, s>>>(fa));
   } else {
     if ((rc = forward_and_inputgrad(c, R, Rp))) return rc;
-    ChainArgs a = base_args(c);
-    zgemm_args(c, a);
-    if ((rc = chain<EPI_STORE>(c, "gemm_z", a, Rp, c->Dp, c->Dp / 16, zgemm_flops(c, R), 0.0))) return rc;
+    if (c->Dp > 128) {
+      if ((rc = zgemm_wide(c, "gemm_z", R, Rp))) return rc;
+    } else {
+      ChainArgs a = base_args(c);
+      zgemm_args(c, a);
+      if ((rc = chain<EPI_STORE>(c, "gemm_z", a, Rp, c->Dp, c->Dp / 16, zgemm_flops(c, R), 0.0))) return rc;
+    }
   }
   const long long m = (long long)R * D;
   RUN(c, s, "export", 0.0, 0.0,

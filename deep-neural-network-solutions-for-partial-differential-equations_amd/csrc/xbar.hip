@@ -19,6 +19,7 @@
 // block is loaded and split once per NT tiles; the four waves of a workgroup
 // run in step over neighbouring rows and share the weight reads through the
 // cache.  No atomics, one fixed summation order: bitwise repeatable.
+// (Dp > 128: the output blocks in passes of 8, netu_xbar_wide_kernel below.)
 //
 // Output: the tile's valid rows of the dense [R, D] result are one contiguous
 // run of floats; the tile goes through a wave-private LDS strip so that run is
@@ -167,6 +168,100 @@ __global__ void __launch_bounds__(64 * XB_WAVES) netu_xbar_kernel(XbarArgs a) {
   }
 }
 
+// Wide contexts (Dp > 128): the Dp / 16 output blocks in passes of XW_TD = 8,
+// pass = blockIdx.y, so a wave holds at most 8 blocks per row tile and the strip
+// stays 16 x (128 + 4) floats.  A pass is the kernel above restricted to its
+// blocks (the last pass may hold fewer: a wave-uniform guard): the same
+// products in the same k order per output element, so bitwise repeatable.  The
+// strip's 128 columns map to xbar columns 128 pass + lc - 1; each row's share
+// is one contiguous run, stored lane-linear.
+constexpr int XW_TD = 8;
+template <int NT>
+__global__ void __launch_bounds__(64 * XB_WAVES) netu_xbar_wide_kernel(XbarArgs a) {
+  constexpr int TD = XW_TD, LDL = 16 * TD + 4;
+  __shared__ float strip[XB_WAVES][16 * LDL];
+  const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long row_base = ((long long)blockIdx.x * XB_WAVES + wave) * (16 * NT);
+  const int K = a.K;
+  const int ob0 = blockIdx.y * TD;
+  const int nbp = min(TD, a.Dp / 16 - ob0);   // this pass's blocks
+  const floatx4 zero4 = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  floatx4 acc[NT][TD];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int o = 0; o < TD; ++o) acc[t][o] = zero4;
+
+  const float* ap[NT];
+  bool av[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const long long row = row_base + 16 * t + i;
+    av[t] = row < a.R;
+    ap[t] = a.Alpha + (size_t)(av[t] ? row : 0) * a.lda + 4 * q;
+  }
+  const float* wp = a.Wt + (size_t)(16 * ob0 + i) * K + 4 * q;
+
+  floatx4 ra[NT][2];
+  auto load_alpha = [&](int k0) {
+    const bool second = k0 + 16 < K;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      ra[t][0] = av[t] ? *(const floatx4*)(ap[t] + k0) : zero4;
+      ra[t][1] = (av[t] && second) ? *(const floatx4*)(ap[t] + k0 + 16) : zero4;
+    }
+  };
+  load_alpha(0);
+  for (int k0 = 0; k0 < K; k0 += 32) {
+    const bool second = k0 + 16 < K;
+    Split3 sa[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sa[t] = split8(ra[t][0], ra[t][1]);
+    if (k0 + 32 < K) load_alpha(k0 + 32);
+#pragma unroll
+    for (int o = 0; o < TD; ++o) {
+      if (o < nbp) {
+        const float* w = wp + (size_t)(16 * o) * K + k0;
+        const floatx4 w0 = *(const floatx4*)w;
+        const floatx4 w1 = second ? *(const floatx4*)(w + 16) : zero4;
+        const Split3 sw = split8(w0, w1);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][o] = mfma_bf(sw.l, sa[t].h, acc[t][o]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][o] = mfma_bf(sw.h, sa[t].l, acc[t][o]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][o] = mfma_bf(sw.m, sa[t].m, acc[t][o]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][o] = mfma_bf(sw.m, sa[t].h, acc[t][o]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][o] = mfma_bf(sw.h, sa[t].m, acc[t][o]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][o] = mfma_bf(sw.h, sa[t].h, acc[t][o]);
+      }
+    }
+  }
+
+  float* st = strip[wave];
+  const int D = a.D;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t > 0) wave_lds_sync();
+#pragma unroll
+    for (int o = 0; o < TD; ++o) *(floatx4*)(st + i * LDL + 16 * o + 4 * q) = acc[t][o];
+    wave_lds_sync();
+    const long long row0 = row_base + 16 * t;
+    const long long left = (long long)a.R - row0;
+    const int nrows = left >= 16 ? 16 : (left > 0 ? (int)left : 0);
+    for (int e = lane; e < nrows * (16 * TD); e += 64) {
+      const int r = e / (16 * TD), lc = e - r * (16 * TD);
+      const int col = 16 * ob0 + lc;   // row-buffer column: 0 = t, 1..D = X
+      if (col >= 1 && col <= D) a.xbar[(size_t)(row0 + r) * D + col - 1] = st[r * LDL + lc];
+    }
+  }
+}
+
 template <int TD>
 int launch_td(const XbarArgs& a, hipStream_t s) {
   constexpr int ROWS = 16 * XB_NT * XB_WAVES;
@@ -190,8 +285,13 @@ int netu_xbar_launch(const XbarArgs& a, hipStream_t s) {
     case 6: return launch_td<6>(a, s);
     case 7: return launch_td<7>(a, s);
     case 8: return launch_td<8>(a, s);
-    default: return -1;
+    default: break;
   }
+  if (a.Dp > 1024) return -1;
+  constexpr int ROWS = 16 * XB_NT * XB_WAVES;
+  const dim3 grid((unsigned)(((long long)a.R + ROWS - 1) / ROWS), (unsigned)((a.Dp / 16 + XW_TD - 1) / XW_TD));
+  netu_xbar_wide_kernel<XB_NT><<<grid, 64 * XB_WAVES, 0, s>>>(a);
+  return 0;
 }
 
 }  // namespace dbsde

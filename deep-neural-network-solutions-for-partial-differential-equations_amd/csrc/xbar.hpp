@@ -16,7 +16,7 @@ struct XbarArgs {
   int lda;
   const float* Wt;      // W^T: [Dp, K] row-major fp32 (the BtZ pack), zero in the padding
   int K;                // multiple of 16
-  int Dp;               // multiple of 16, <= 128
+  int Dp;               // multiple of 16, <= 1024 (above 128: output blocks in passes of 8)
   int R, D;             // valid rows, state dimension (D + 1 <= Dp)
   float* xbar;          // [R, D] dense
 };

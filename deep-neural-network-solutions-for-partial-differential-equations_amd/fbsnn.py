@@ -181,7 +181,7 @@ class FBSNN(ABC):
         self.correlation_matrix = self.generate_correlation_matrix(self.solver.nb)
         self._L = None if correlation_type == "no_correlation" else np.linalg.cholesky(self.correlation_matrix)
         if self._L is not None and spec.kind == "diag":
-            self.solver.set_corr(self._L)       # device mode: L staged in LDS by the path kernel
+            self.solver.set_corr(self._L)       # device mode: the path kernels' copy of L (nb <= 1022)
         self.rank, self.world = _world()
 
     # ------------------------------------------------------------------ problem

@@ -420,7 +420,8 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
     Philox draws -- the same draws for every point (common random numbers).
     spec: a ProblemSpec with phi_zz == 0 (HJB: hjb_mc); t [P], X [P, D] float32
     cuda tensors (Heston: D = 2k, [S.., v..]); L: an optional [D, D] lower
-    Cholesky factor (diag problems, D <= 128).  Returns (value [P, 1], stderr
+    Cholesky factor (diag problems, D <= 128 here, although the training
+    step's set_corr takes D <= 1022).  Returns (value [P, 1], stderr
     [P, 1], delta [P, D] or None); delta is the pathwise estimator (diag only)."""
     if spec.phi_zz != 0:
         raise ValueError("mc_value needs a linear problem (phi_zz == 0); the HJB comparator is hjb_mc")

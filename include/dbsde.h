@@ -103,7 +103,8 @@ typedef struct dbsde_config {
   int mode;          /* DBSDE_MODE_*                                   */
   int activation;    /* DBSDE_ACT_*                                    */
   int n_layers;      /* len(layers), 4..9                              */
-  int layers[16];    /* [D+1, W1, ..., Wk, 1]                          */
+  int layers[16];    /* [D+1, W1, ..., Wk, 1]; D <= 1022 (the padded   */
+                     /* row pad16(D + 2) <= 1024), else DBSDE_EINVAL   */
   dbsde_problem problem;
   float T;           /* terminal time                                  */
   int device;        /* HIP device ordinal                             */
@@ -155,8 +156,9 @@ int dbsde_brownian_dim(const dbsde_ctx* ctx);
 /*
  * Cholesky factor of the increments' correlation matrix for the DEVICE mode
  * (with_corr_high_dimension_pde.py:339-341: dW = L (sqrt(dt) z)).  L is a host
- * [n, n] row-major lower-triangular fp32 matrix, n = dbsde_brownian_dim <= 128;
- * the context keeps a device copy (staged in LDS by the path kernel).  L ==
+ * [n, n] row-major lower-triangular fp32 matrix, n = dbsde_brownian_dim <= 1022;
+ * the context keeps a device copy (n <= 128: held in registers by the path
+ * kernel; above: streamed by the triangular increment GEMM).  L ==
  * NULL clears it.  Parity-mode batches (W != NULL) already carry correlated W
  * and ignore L.  DIAG problems only.
  */
@@ -270,7 +272,9 @@ int dbsde_net_u_xvjp(dbsde_ctx* ctx, const float* params, int R, const float* t,
  * theta = u_t, which dbsde_net_u / dbsde_net_u_xvjp do not).  Forward (Taylor-mode)
  * propagation in split-bf16 matrix products with fp32 accumulation; nothing is stored per
  * (point, direction) row, and rows are launched DBSDE_JET_CAP (default 65536, read at
- * dbsde_create) at a time.  Hidden widths above 256 are not supported (EINVAL). */
+ * dbsde_create) at a time.  Hidden widths above 256 are not supported (EINVAL).  A wave
+ * stages 16 (Dp + 4 + 2 ldw) floats of LDS (97 KB at D = 1022, width 256); a combination
+ * above the CU's 160 KB is EINVAL. */
 int dbsde_net_u_jet(dbsde_ctx* ctx, const float* params, int R, const float* t, const float* X,
                     int nd, const float* V, float* d1, float* d2);
 
