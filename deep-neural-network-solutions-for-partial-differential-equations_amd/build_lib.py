@@ -17,10 +17,11 @@ CSRC = os.path.join(HERE, "csrc")
 # built with VGPR-form MFMA (see csrc/tnw.hip); everything else (its split-bf16
 # form tnwx3.hip included: accumulators in AGPRs; xbar.hip: net_u's input
 # cotangent; jet.hip: the forward jets and the PDE residual; mc.hip: the
-# Feynman-Kac Monte-Carlo comparator) with the defaults
+# Feynman-Kac Monte-Carlo comparator; projw.hip: the NAIS projection at hidden
+# widths above 128) with the defaults
 UNITS = [("step.hip", []), ("net.hip", []), ("rollout.hip", []), ("vec.hip", []), ("phase2.hip", []), ("phasecs.hip", []),
          ("evals.hip", []), ("mc.hip", []), ("tnw.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=true"]), ("tnwx3.hip", []), ("xbar.hip", []),
-         ("jet.hip", [])]
+         ("jet.hip", []), ("projw.hip", [])]
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))] + \
     [os.path.join(ROOT, "include", "dbsde.h")]
 OUT = os.path.join(HERE, "lib", "libdbsde.so")

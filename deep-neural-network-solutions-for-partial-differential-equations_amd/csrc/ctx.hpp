@@ -24,6 +24,7 @@
 #include "phase.hpp"
 #include "phase2.hpp"
 #include "phasecs.hpp"
+#include "projw.hpp"
 
 using namespace dbsde;
 
@@ -152,6 +153,12 @@ struct dbsde_ctx {
   double* dot_part = nullptr;     // <Abar_j, R_j> partials from the gradient finalize (one per 64 elements)
   int dot_nblk = 0;               // partials slots per block (stride)
   int dot_nused = 0;              // partials the finalize writes (tilefin: one per 256 tile elements)
+  // hidden widths above NAIS_LMAX: the matrix-core projection kernels
+  // (projw.hpp) with one reduced |R_j|_F^2 / <Abar_j, R_j> per block
+  bool proj_wide = false;
+  double* proj_sq = nullptr;      // [K] |R_j|_F^2
+  float** d_sbuf = nullptr;       // S_j = Rbar_j + Rbar_j^T of the wide adjoint
+  double* proj_dot = nullptr;     // [K] <Abar_j, R_j>
   unsigned char* d_used = nullptr;
   PackDesc* d_prep = nullptr;
   int n_prep = 0;

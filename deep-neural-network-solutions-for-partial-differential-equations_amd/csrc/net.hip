@@ -218,7 +218,9 @@ int build_net(dbsde_ctx* c) {
   if (c->rho != 0.f)
     for (int j = 2; j < n - 1; ++j)
       if (L[j] != L[1]) return fail(c, DBSDE_EINVAL, "residual modes need equal hidden widths");
-  if (c->proj && L[1] > NAIS_LMAX) return fail(c, DBSDE_EINVAL, "NAIS projection supports hidden width <= 128");
+  if (c->proj && L[1] > NAIS_WIDE_LMAX)
+    return fail(c, DBSDE_EINVAL, "NAIS projection supports hidden width <= 1024");
+  c->proj_wide = c->proj && L[1] > NAIS_LMAX;
   c->nparams = off;
   c->used.assign(off, 1);
   if (g.mode == DBSDE_MODE_NAIS_NET) {
@@ -323,18 +325,26 @@ int build_buffers(dbsde_ctx* c) {
   const int LW = c->L[1];
   if (c->proj) {
     if ((rc = dalloc_t(c, &c->norms, (size_t)K + 1))) return rc;
-    std::vector<float*> hr(K), ha(K), hs(K);
+    std::vector<float*> hr(K), ha(K), hs(K), hb(K, nullptr);
     std::vector<long long> hw(K);
     for (int j = 1; j <= K; ++j) {
       if ((rc = dalloc_t(c, &c->rtr[j], (size_t)LW * LW))) return rc;
       if ((rc = dalloc_t(c, &c->abar[j], (size_t)LW * LW))) return rc;
       if ((rc = dalloc_t(c, &hs[j - 1], (size_t)LW * LW))) return rc;
+      if (c->proj_wide && (rc = dalloc_t(c, &hb[j - 1], (size_t)LW * LW))) return rc;
       hr[j - 1] = c->rtr[j];
       ha[j - 1] = c->abar[j];
       hw[j - 1] = c->B[j - 1].w;
     }
+    // (the wide kernels' triangle of 64 x 64 tiles is the smaller count)
     if ((rc = dalloc_t(c, &c->proj_part, (size_t)K * std::max((LW * LW + 255) / 256, ((LW + 15) / 16) * ((LW + 15) / 16)))))
       return rc;
+    if (c->proj_wide) {
+      if ((rc = dalloc_t(c, &c->proj_sq, K))) return rc;
+      if ((rc = dalloc_t(c, &c->proj_dot, K))) return rc;
+      if ((rc = dalloc_t(c, &c->d_sbuf, K))) return rc;
+      HIPC(c, hipMemcpy(c->d_sbuf, hb.data(), K * sizeof(float*), hipMemcpyHostToDevice));
+    }
     c->dot_nblk = (LW * LW + 63) / 64;
     c->dot_nused = c->dot_nblk;   // tnw layouts override below
     if ((rc = dalloc_t(c, &c->dot_part, (size_t)K * c->dot_nblk))) return rc;
@@ -417,16 +427,19 @@ int build_buffers(dbsde_ctx* c) {
   for (int j = 1; j <= K; ++j) {
     const Lin& b = c->B[j - 1];
     if (c->proj) {
-      const int nblk = ((LW + 15) / 16) * ((LW + 15) / 16);
+      // |R_j|_F^2: this block's rtr partials, or (wide) the one sum
+      // projw_forward_launch reduced them to, as a single partial
+      const int nblk = c->proj_wide ? 1 : ((LW + 15) / 16) * ((LW + 15) / 16);
+      const double* pn = c->proj_wide ? c->proj_sq + (j - 1) : c->proj_part + (size_t)(j - 1) * nblk;
       PackDesc d = mk_desc(c->rtr[j], LW, c->Bf[j], c->Wp[j - 1], LW, LW, 0, PK_NEGPROJ);
-      d.proj = c->proj_part + (size_t)(j - 1) * nblk;
+      d.proj = pn;
       d.proj_n = nblk;
       d.proj_norm = nullptr;
       keep(d);
       d.proj_norm = c->norms + (j - 1);
       P.push_back(frag(d, c->imgF[j], TW, TW, 0, 0));
       d = mk_desc(c->rtr[j], LW, c->Bb[j], c->Wp[j], LW, LW, 1, PK_NEGPROJ);
-      d.proj = c->proj_part + (size_t)(j - 1) * nblk;
+      d.proj = pn;
       d.proj_n = nblk;
       d.proj_norm = nullptr;
       P.push_back(frag(d, c->imgB[j], TW, TW, 0, 0));

@@ -12,7 +12,9 @@
 //   weight-grad split-K TN GEMMs into slabs, fixed-order slab sums, NAIS adjoint
 // State dimensions above 126 (Dp > 128) run this per-layer sequence with the Z
 // GEMM over column tiles (zgemm_wide) and the residual epilogue as a row kernel
-// behind it (fused.hpp zrow_cotan_kernel); DESIGN 3.6.
+// behind it (fused.hpp zrow_cotan_kernel); DESIGN 3.6.  NAIS hidden widths
+// above 128 run it too, with the projection and its adjoint on the
+// matrix-core kernels of projw.hip.
 //
 // This unit instantiates the kernels of kernels.hpp, fused.hpp, phase.hpp,
 // chainx3.hpp and tnx3.hpp.
@@ -151,10 +153,37 @@ void x3_weights(dbsde_ctx* c, ChainArgs& a, const float* img, int tout, int ti) 
   a.x3_ti = ti;
 }
 
+// arguments of the wide projection kernels (projw.hpp)
+ProjWideArgs projw_args(dbsde_ctx* c, const float* params, float* grad) {
+  ProjWideArgs a{};
+  a.params = params;
+  a.woffs = c->d_woffs;
+  a.L = c->L[1];
+  a.K = c->K;
+  a.rtr = c->d_rtr;
+  a.wsnap = c->d_wsnap;
+  a.abar = c->d_abar;
+  a.sbuf = c->d_sbuf;
+  a.part = c->proj_part;
+  a.npart = projw_tri_tiles(a.L);
+  a.sq = c->proj_sq;
+  a.dot_part = c->dot_part;
+  a.dot_nblk = c->dot_nblk;
+  a.dot_nused = c->dot_nused;
+  a.dot = c->proj_dot;
+  a.grad = grad;
+  return a;
+}
+
 int prep_weights(dbsde_ctx* c, const float* params) {
   hipStream_t s = c->stream;
   const int LW = c->L[1];
-  if (c->proj) {
+  if (c->proj_wide) {
+    int ok = 0;
+    const ProjWideArgs pa = projw_args(c, params, nullptr);
+    RUN(c, s, "rtr_wide", 2.0 * c->K * LW * (double)LW * LW, 0.0, ok = projw_forward_launch(pa, s));
+    if (ok) return fail(c, DBSDE_EINVAL, "internal: wide projection geometry");
+  } else if (c->proj) {
     const double fl = 2.0 * c->K * LW * (double)LW * LW;
     const int nblk = ((LW + 15) / 16) * ((LW + 15) / 16);
     RUN(c, s, "rtr", fl, 0.0,
@@ -258,7 +287,14 @@ int finalize_grads(dbsde_ctx* c, const float* params, float* grad, const double*
         slabsum_kernel<<<dim3(c->fin_blocks, c->n_fin), 256, 0, s>>>(c->d_fin, grad, c->tn_splits_cur, loss_part,
                                                                       nloss, loss));
   }
-  if (c->proj) {
+  if (c->proj_wide) {
+    if (fuse) return fail(c, DBSDE_EINVAL, "internal: fused update at a wide projection");
+    const int LW = c->L[1];
+    int ok = 0;
+    const ProjWideArgs pa = projw_args(c, params, grad);
+    RUN(c, s, "proj_backward_wide", 2.0 * c->K * LW * (double)LW * LW, 0.0, ok = projw_backward_launch(pa, s));
+    if (ok) return fail(c, DBSDE_EINVAL, "internal: wide projection geometry");
+  } else if (c->proj) {
     const int LW = c->L[1];
     const int ntile = ((LW + 15) / 16) * ((LW + 15) / 16);
     RUN(c, s, "proj_backward", 2.0 * c->K * LW * (double)LW * LW, 0.0,

@@ -104,7 +104,9 @@ typedef struct dbsde_config {
   int activation;    /* DBSDE_ACT_*                                    */
   int n_layers;      /* len(layers), 4..9                              */
   int layers[16];    /* [D+1, W1, ..., Wk, 1]; D <= 1022 (the padded   */
-                     /* row pad16(D + 2) <= 1024), else DBSDE_EINVAL   */
+                     /* row pad16(D + 2) <= 1024), else DBSDE_EINVAL;  */
+                     /* NAIS_NET / NAISNET: the (equal) hidden widths  */
+                     /* W1 = .. = Wk <= 1024, else DBSDE_EINVAL        */
   dbsde_problem problem;
   float T;           /* terminal time                                  */
   int device;        /* HIP device ordinal                             */
