@@ -18,6 +18,10 @@ constexpr int LBFGS_HMAX = 128;   // history entries per call (torch's default h
 
 enum VecOp { VEC_DOT = 0, VEC_ASUM = 1, VEC_AMAX = 2 };
 
+// max that keeps a NaN from either side (fmax returns the other operand):
+// AMAX of a vector holding a NaN is NaN, as torch's tensor.abs().max()
+__device__ inline double nanmax(double a, double b) { return (a > b || a != a) ? a : b; }
+
 // per-block partials of sum a b / sum |a| / max |a| (fp64, fixed order)
 __global__ void __launch_bounds__(256) vec_reduce_kernel(int op, const float* a, const float* b, long long n,
                                                          double* part) {
@@ -27,12 +31,12 @@ __global__ void __launch_bounds__(256) vec_reduce_kernel(int op, const float* a,
     const double x = a[i];
     if (op == VEC_DOT) s += x * (double)b[i];
     else if (op == VEC_ASUM) s += fabs(x);
-    else s = fmax(s, fabs(x));
+    else s = nanmax(s, fabs(x));
   }
   red[threadIdx.x] = s;
   __syncthreads();
   for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] = op == VEC_AMAX ? fmax(red[threadIdx.x], red[threadIdx.x + k])
+    if (threadIdx.x < k) red[threadIdx.x] = op == VEC_AMAX ? nanmax(red[threadIdx.x], red[threadIdx.x + k])
                                                            : red[threadIdx.x] + red[threadIdx.x + k];
     __syncthreads();
   }
@@ -41,11 +45,11 @@ __global__ void __launch_bounds__(256) vec_reduce_kernel(int op, const float* a,
 __global__ void __launch_bounds__(256) vec_reduce_final_kernel(int op, const double* part, int nparts, double* out) {
   __shared__ double red[256];
   double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) s = op == VEC_AMAX ? fmax(s, part[i]) : s + part[i];
+  for (int i = threadIdx.x; i < nparts; i += 256) s = op == VEC_AMAX ? nanmax(s, part[i]) : s + part[i];
   red[threadIdx.x] = s;
   __syncthreads();
   for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] = op == VEC_AMAX ? fmax(red[threadIdx.x], red[threadIdx.x + k])
+    if (threadIdx.x < k) red[threadIdx.x] = op == VEC_AMAX ? nanmax(red[threadIdx.x], red[threadIdx.x + k])
                                                            : red[threadIdx.x] + red[threadIdx.x + k];
     __syncthreads();
   }

@@ -292,7 +292,8 @@ class NativeSolver:
     # ------------------------------------------------------------------ L-BFGS vector primitives
     def vec_reduce(self, op, a, b=None):
         """Fixed-order fp64 sum a.b ("dot"), sum |a| ("asum") or max |a| ("amax")
-        of device fp32 vectors, returned as a Python float (syncs)."""
+        of device fp32 vectors, returned as a Python float (syncs).  A NaN
+        element makes each of them NaN ("amax" as tensor.abs().max())."""
         self._check_tensor(a, "a")
         self._check_tensor(b, "b", a.numel() if b is not None else None)
         out = ctypes.c_double()

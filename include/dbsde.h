@@ -367,6 +367,10 @@ int dbsde_train_step(dbsde_ctx* ctx, float* params, const dbsde_batch* batch, fl
 #define DBSDE_VEC_DOT 0    /* sum_i a_i b_i */
 #define DBSDE_VEC_ASUM 1   /* sum_i |a_i|   (b unused) */
 #define DBSDE_VEC_AMAX 2   /* max_i |a_i|   (b unused) */
+/* A NaN element makes every one of the three results NaN.  AMAX propagates it
+ * as torch's tensor.abs().max() does (not C fmax, which drops it): torch's
+ * L-BFGS stops on `flat_grad.abs().max() <= tolerance_grad`, which is False
+ * for a NaN gradient, so a NaN gradient must not read as amax 0 = converged. */
 int dbsde_vec_reduce(dbsde_ctx* ctx, int op, const float* a, const float* b, long long n, double* result);
 /* z = alpha x + beta y in fp32 (z may alias x or y; y may be NULL when beta == 0) */
 int dbsde_vec_axpby(dbsde_ctx* ctx, float* z, const float* x, const float* y, long long n, float alpha, float beta);

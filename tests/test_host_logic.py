@@ -233,6 +233,52 @@ def test_lbfgs_driver_matches_torch_lbfgs(lr):
     assert abs(st["n_iter"] - topt.state[ref]["n_iter"]) <= 2
 
 
+def test_lbfgs_driver_does_not_take_a_nan_gradient_for_converged():
+    """torch tests `flat_grad.abs().max() <= tolerance_grad`, which is False for
+    a NaN gradient: LBFGS.step goes on (and evaluates the closure again).
+    _lbfgs_step over a vec_reduce whose AMAX propagates NaN (the contract of
+    DBSDE_VEC_AMAX, include/dbsde.h) does the same, evaluation for evaluation;
+    an AMAX that dropped the NaN (C fmax) would return after the first one."""
+    pkg = load_pkg()
+    n = 6
+    x0 = torch.linspace(-1.0, 1.0, n)
+
+    def f(x):      # sqrt(x_0 - 2) is NaN here: the gradient's first element is NaN, the rest finite
+        return torch.sum(x ** 2) + torch.sqrt(x[0] - 2.0) * 0.0
+
+    ref = x0.clone().requires_grad_(True)
+    topt = torch.optim.LBFGS([ref], lr=1.0)
+
+    def tclosure():
+        topt.zero_grad()
+        loss = f(ref)
+        loss.backward()
+        return loss
+
+    topt.step(tclosure)
+    assert topt.state[ref]["func_evals"] > 1
+
+    obj = object.__new__(pkg.CallOption)
+    obj.device = torch.device("cpu")
+    obj.params = x0.clone()
+    obj.grad = torch.zeros(n)
+    obj.solver = _CpuVecSolver()
+    assert np.isnan(obj.solver.vec_reduce("amax", torch.tensor([1.0, float("nan"), 0.5])))
+
+    def closure():
+        x = obj.params.clone().requires_grad_(True)
+        loss = f(x)
+        loss.backward()
+        obj.grad.copy_(x.grad)
+        return float(loss)
+
+    st = obj._lbfgs_state(1.0)
+    obj._lbfgs_step(st, closure)
+    assert torch.isnan(obj.grad).any()
+    assert st["func_evals"] == topt.state[ref]["func_evals"] > 1
+    assert st["n_iter"] == topt.state[ref]["n_iter"]
+
+
 def _rne16(x):
     """fp32 -> the nearest bf16 value (ties to even), as fp32 (v_cvt_pk_bf16_f32)."""
     u = x.view(np.uint32).astype(np.uint64)
