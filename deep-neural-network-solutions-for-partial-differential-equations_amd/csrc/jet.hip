@@ -350,7 +350,9 @@ __device__ __forceinline__ float clamp100(float x) { return fminf(fmaxf(x, -100.
 
 // direction 0 = e_t; direction 1 + j = column j of the diffusion matrix:
 // DIAG diag(sig_a X + sig_b) . L; Heston Sigma_j . (1, 1)^T in the (S_j, v_j)
-// plane with the rollout's sqrt(max(v, 1e-8)) and +-100 clamps (paths.hpp)
+// plane with the rollout's sqrt(max(v, 1e-8)) and +-100 clamps (paths.hpp),
+// and with a factor L between the assets column j of Sigma(x) . L: for every
+// asset i >= j the (S_i, v_i) entries of Sigma_i . (1, 1)^T times L[i][j]
 __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
   const int ld = a.D + 1;
   const long long n = (long long)a.np * a.nd * ld;
@@ -368,11 +370,13 @@ __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
     const int jb = j - 1, d = c - 1;
     if (a.heston) {
       const int k = a.nb;
-      if (d == jb || d == k + jb) {
-        const float S = x[jb], vv = x[k + jb];
+      const int i = d < k ? d : d - k;   // the asset of column d
+      if (a.Lt ? i >= jb : i == jb) {
+        const float S = x[i], vv = x[k + i];
         const float sv = sqrtf(fmaxf(vv, 1e-8f));
         const float sigS = sv * S, sigV = a.pr.h_sigma * sv;
-        v = d == jb ? clamp100(sigS) + clamp100(a.pr.h_rho * sigV) : clamp100(a.pr.h_rho * sigS) + clamp100(sigV);
+        v = d < k ? clamp100(sigS) + clamp100(a.pr.h_rho * sigV) : clamp100(a.pr.h_rho * sigS) + clamp100(sigV);
+        if (a.Lt) v *= a.Lt[(size_t)jb * k + i];   // L[i][jb]
       }
     } else {
       const float l = a.Lt ? (jb <= d ? a.Lt[(size_t)jb * a.nb + d] : 0.f) : (d == jb ? 1.f : 0.f);
@@ -663,7 +667,7 @@ int dbsde_pde_residual(dbsde_ctx* c, const float* params, int R, const float* t,
     pa.D = D;
     pa.nb = c->nb;
     pa.nd = nd;
-    pa.Lt = c->heston ? nullptr : c->Lt;
+    pa.Lt = c->Lt;
     pa.X = X;
     pa.r0 = r0;
     pa.np = np;

@@ -904,6 +904,93 @@ __global__ void __launch_bounds__(256) rollout_heston_kernel(RolloutArgs p) {
   }
 }
 
+// --------------------------------------------------------------------------
+// Correlated k-asset Heston in device mode (dbsde_set_corr on a Heston
+// context: the assets' Brownian motions are dW = L (sqrt(dt) z), L [k, k]),
+// two passes for every k <= 511:
+//   pass 1: rollout_corrw_kernel with nb = k.  Its Philox key (seed, offset,
+//     global path, step block, coordinate i) is rollout_heston_kernel's, its
+//     summation order is the one documented there, and its store
+//     sdw[row, 1 + i] is the S_i column of a Heston row (D = 2 k), which parks
+//     asset i's increment of step n in row n.
+//   pass 2 (rollout_heston_chain_kernel): thread per (path, asset) runs
+//     rollout_heston_kernel's step (the same rn_* operations, correctly rounded
+//     sqrt, +-100 clamps and fp64 time grid, so with L = I the paths are
+//     bit-identical to the uncorrelated kernel's), reading its increments
+//     RC_AHEAD rows ahead of the chain, and overwrites sdw[row, 1 + i] and
+//     sdw[row, 1 + k + i] with the Y-tilde term.  A thread reads and writes
+//     only its own asset's columns (asset 0's thread also t and the constant
+//     1), so no ordering between threads is needed.
+// Workgroup size HC_THREADS = 256.  rollout_chain_kernel's 64 (its float4 row
+// stores are bound by each CU's store issue, so it spreads them over every CU)
+// was measured here too and does not carry over: a wave's 64 threads store 256
+// contiguous bytes per instruction, and at M = 1024, N = 100 the launch takes
+// 41.7 / 80.2 / 251 us at k = 50 / 130 / 511 with 64 threads, 40.3 / 75.1 / 246
+// with 128 and 40.2 / 75.6 / 224 with 256 (profiles/heston_corr_times.json,
+// DESIGN 3.7).
+// The fetch takes pass 1 into W_out and then corrw_fetch_kernel.
+// --------------------------------------------------------------------------
+constexpr int HC_THREADS = 256;
+template <bool HOST_T = false>
+__global__ void __launch_bounds__(256) rollout_heston_chain_kernel(RolloutArgs p) {
+  const int k = p.nb;
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= p.M * k) return;
+  const int m = gid / k, i = gid - m * k;
+  const int N1 = p.N + 1;
+  const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
+  float S = xi[i], v = xi[k + i];
+  const double dt64 = (double)p.T / (double)p.N;
+  double tacc = 0.0;
+  float t0 = 0.0f;
+  if constexpr (HOST_T) t0 = p.t[(size_t)m * N1];
+  const size_t r0 = (size_t)m * N1;
+  for (int n0 = 0; n0 < p.N; n0 += RC_AHEAD) {
+    float dw[RC_AHEAD];
+#pragma unroll
+    for (int a = 0; a < RC_AHEAD; ++a) dw[a] = n0 + a < p.N ? p.sdw[(r0 + n0 + a) * p.ldx + 1 + i] : 0.f;
+#pragma unroll
+    for (int a = 0; a < RC_AHEAD; ++a) {
+      const int n = n0 + a;
+      if (n >= p.N) break;
+      tacc += dt64;
+      float t1 = (float)tacc;
+      if constexpr (HOST_T) t1 = p.t[(size_t)m * N1 + n + 1];
+      float* xr = p.xin + (r0 + n) * p.ldx;
+      float* sr = p.sdw + (r0 + n) * p.ldx;
+      xr[1 + i] = S;
+      xr[1 + k + i] = v;
+      if (i == 0) {
+        xr[0] = t0;
+        xr[p.D + 1] = 1.0f;
+      }
+      const float dt = rn_sub(t1, t0);
+      const float muS = clamp100(rn_mul(p.mu_a, S));
+      const float muV = clamp100(rn_mul(p.kappa, rn_sub(p.theta, v)));
+      const float sv = sqrtf(fmaxf(v, 1e-8f));   // correctly rounded, as in rollout_heston_kernel
+      const float sigS = rn_mul(sv, S), sigV = rn_mul(p.hsig, sv);
+      const float d00 = clamp100(sigS), d11 = clamp100(sigV);
+      const float d01 = clamp100(rn_mul(p.rho, sigV)), d10 = clamp100(rn_mul(p.rho, sigS));
+      const float w = dw[a];
+      sr[1 + i] = rn_add(rn_mul(d00, w), rn_mul(d01, w));
+      sr[1 + k + i] = rn_add(rn_mul(d10, w), rn_mul(d11, w));
+      S = rn_add(rn_add(S, rn_mul(muS, dt)), rn_mul(rn_add(d00, d01), w));
+      v = rn_add(rn_add(v, rn_mul(muV, dt)), rn_mul(rn_add(d10, d11), w));
+      t0 = t1;
+    }
+  }
+  float* xr = p.xin + (r0 + p.N) * p.ldx;   // n = N
+  float* sr = p.sdw + (r0 + p.N) * p.ldx;
+  xr[1 + i] = S;
+  xr[1 + k + i] = v;
+  sr[1 + i] = 0.0f;
+  sr[1 + k + i] = 0.0f;
+  if (i == 0) {
+    xr[0] = t0;
+    xr[p.D + 1] = 1.0f;
+  }
+}
+
 // Q3 (D == 1): S_n = sum over paths of sdw[m, n]   (1d_BSPDE_case.py:271-273)
 __global__ void __launch_bounds__(256) q3_sum_kernel(const float* sdw, int ldx, int M, int N, float* S) {
   const int n = blockIdx.x;

@@ -4,6 +4,8 @@
 // dbsde_set_corr, dbsde_brownian).
 // Correlated device mode: rollout_corr_kernel up to nb = 128 (L in registers),
 // above it the increment GEMM rollout_corrw_kernel followed by the Euler chains.
+// Correlated Heston (L between the k assets): the increment GEMM at every k,
+// then rollout_heston_chain_kernel.
 #include <hip/hip_runtime.h>
 
 // a prefetched rollout runs on the next chunked step's second stream
@@ -90,6 +92,17 @@ void launch_corr(const RolloutArgs& ra, hipStream_t s) {
   }
 }
 
+// workgroup size of rollout_heston_chain_kernel: HC_THREADS; DBSDE_HC_THREADS =
+// 64 or 128 (read once) is the measurement switch of tools/heston_corr_profile.py
+int heston_chain_threads() {
+  static const int n = [] {
+    const char* e = getenv("DBSDE_HC_THREADS");
+    const int v = e ? atoi(e) : HC_THREADS;
+    return v == 64 || v == 128 ? v : HC_THREADS;
+  }();
+  return n;
+}
+
 // Euler-Maruyama paths (ra.out == PATH_ROLLOUT) or the device fetch_minibatch
 // (PATH_FETCH_*): Heston, Cholesky-correlated device mode, or diagonal
 // side: a prefetched rollout running beside other work (the two-pass form's
@@ -99,18 +112,24 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
   const char* name = ra.out == PATH_ROLLOUT ? "rollout" : "brownian";
   const double steps = (double)ra.M * ra.N;
   const double bytes = ra.out == PATH_ROLLOUT ? 4.0 * steps * (2.0 * ra.D + (ra.W ? ra.nb : 0)) : 4.0 * steps * ra.nb;
-  if (c->heston) {
-    const int nthr = ra.M * ra.nb;
-    RUN(c, s, name, 0.0, bytes, rollout_heston_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
-  } else if (c->Lt && !ra.W && ra.nb > CP_NBMAX) {
-    // wide correlated device mode (paths.hpp): the triangular GEMM dW = L (sqrt(dt) z)
-    // over (path group, step block), then the Euler chains or the fetch sums
-    if (ra.ldx % 4 != 0 || ra.nb > CW_OB * 8 * 16 || ra.nb != ra.D)
+  if (c->Lt && !ra.W && (c->heston || ra.nb > CP_NBMAX)) {
+    // wide correlated device mode, and correlated Heston at every k (paths.hpp):
+    // the triangular GEMM dW = L (sqrt(dt) z) over (path group, step block),
+    // then the Euler chains or the fetch sums
+    if (ra.ldx % 4 != 0 || ra.nb > CW_OB * 8 * 16 || ra.nb * (c->heston ? 2 : 1) != ra.D)
       return fail(c, DBSDE_EINVAL, "internal: wide correlated rollout geometry");
     const dim3 g((ra.M + CW_PATHS - 1) / CW_PATHS, (ra.N + 3) / 4);
     const double fl = 2.0 * steps * ra.nb * ra.nb / 2;
     RUN(c, s, "corr_increments", fl, 4.0 * steps * ra.nb, rollout_corrw_kernel<<<g, CW_THREADS, 0, s>>>(ra));
-    if (ra.out == PATH_ROLLOUT) {
+    if (ra.out == PATH_ROLLOUT && c->heston) {
+      // reads the k increments, writes the 2k columns of xin and of sdw
+      const int nthr = ra.M * ra.nb, hc = heston_chain_threads();
+      const unsigned gb = (unsigned)((nthr + hc - 1) / hc);
+      if (ra.t)
+        RUN(c, s, name, 0.0, bytes + 4.0 * steps * ra.nb, rollout_heston_chain_kernel<true><<<gb, hc, 0, s>>>(ra));
+      else
+        RUN(c, s, name, 0.0, bytes + 4.0 * steps * ra.nb, rollout_heston_chain_kernel<false><<<gb, hc, 0, s>>>(ra));
+    } else if (ra.out == PATH_ROLLOUT) {
       const int chains = ra.M * (ra.ldx / 4);
       const unsigned gb = (unsigned)((chains + RC_THREADS - 1) / RC_THREADS);
       if (ra.t)
@@ -121,6 +140,10 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
       const long long nthr = (long long)ra.M * ra.nb;
       RUN(c, s, name, 0.0, bytes, corrw_fetch_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, s>>>(ra));
     }
+  } else if (c->heston) {
+    // parity-mode batches (the caller's W), and contexts without a factor
+    const int nthr = ra.M * ra.nb;
+    RUN(c, s, name, 0.0, bytes, rollout_heston_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
   } else if (c->Lt && !ra.W) {
     if (ra.ldx > cp_srow((ra.nb + 15) / 16) || ra.ldx % 4 != 0)
       return fail(c, DBSDE_EINVAL, "internal: correlated rollout row staging");
@@ -324,7 +347,7 @@ int dbsde_set_corr(dbsde_ctx* c, const float* L, int n) {
     }
     return DBSDE_OK;
   }
-  if (c->heston) return fail(c, DBSDE_EINVAL, "dbsde_set_corr: correlated increments are for DIAG problems");
+  // (Heston: nb = k = D / 2 <= 511, the assets' Brownian motions)
   if (n != c->nb) return fail(c, DBSDE_EINVAL, "dbsde_set_corr: L must be [nb, nb], nb = the Brownian dimension");
   std::vector<float> lt((size_t)n * n, 0.f);
   for (int d = 0; d < n; ++d)

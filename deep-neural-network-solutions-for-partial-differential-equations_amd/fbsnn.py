@@ -180,8 +180,10 @@ class FBSNN(ABC):
         self.correlation_type = correlation_type
         self.correlation_matrix = self.generate_correlation_matrix(self.solver.nb)
         self._L = None if correlation_type == "no_correlation" else np.linalg.cholesky(self.correlation_matrix)
-        if self._L is not None and spec.kind == "diag":
-            self.solver.set_corr(self._L)       # device mode: the path kernels' copy of L (nb <= 1022)
+        if self._L is not None:
+            # device mode and pde_residual: the kernels' copy of L (diagonal problems nb <= 1022;
+            # Heston: L [k, k] between the assets' Brownian motions, k <= 511)
+            self.solver.set_corr(self._L)
         self.rank, self.world = _world()
 
     # ------------------------------------------------------------------ problem
@@ -399,7 +401,11 @@ class FBSNN(ABC):
         problem_spec(), or a mismatching one) evaluates mu_tf / sigma_tf /
         phi_tf in torch and passes the columns of the diffusion its rollout
         uses (sigma_tf, times the Cholesky factor when correlated) through
-        solver.net_u_jet; the contraction is the same."""
+        solver.net_u_jet; the contraction is the same.  The native context
+        holds the object's Cholesky factor (set at construction), so a
+        correlated object -- a diagonal problem, or a k-asset Heston with L
+        between its assets -- gets the residual of the correlated PDE: the
+        diffusion columns are those of sigma(x) . L."""
         t, X = self._points(t, X)
         R, D = X.shape
         if self.native_coefficients:
@@ -673,9 +679,9 @@ class FBSNN(ABC):
         loss+grad, all-reduce, clip + optimizer.  No host synchronisation;
         returns the device loss.  next_seed: the seed of the following
         iteration, whose rollout is then prefetched to overlap this one
-        (dbsde_prefetch); the numbers are the same either way."""
-        if self._L is not None and self.spec.kind != "diag":
-            raise NotImplementedError("device-mode correlated increments are implemented for diagonal problems")
+        (dbsde_prefetch); the numbers are the same either way.  A correlated
+        Heston object (L between its k assets) runs here as the correlated
+        basket does."""
         p0, ml = self._local_slice(self.M)
         xi = self._device_xi(p0, ml)
         lbfgs = opt_state["kind"] == "LBFGS"
@@ -826,7 +832,10 @@ class FBSNN(ABC):
         (value [P, 1], stderr [P, 1], delta [P, D] or None).  Linear problems
         only: phi_zz != 0 (HJB) raises ValueError (use hjb_mc), and so does a
         problem running its own coefficient methods (the generic path), whose
-        SDE the kernel does not know."""
+        SDE the kernel does not know.  A Heston object's comparator simulates
+        INDEPENDENT assets even when the object is correlated (dbsde_mc_value
+        takes no factor for Heston): its value is then not the trained
+        network's target."""
         if not self.native_coefficients:
             raise ValueError(f"{type(self).__name__} runs its own coefficient methods ({self.generic_reason}); "
                              "mc_value needs a problem_spec() the native step runs")

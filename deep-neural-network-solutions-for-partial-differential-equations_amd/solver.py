@@ -330,7 +330,8 @@ class NativeSolver:
 
     # ------------------------------------------------------------------ Brownian increments
     def set_corr(self, L):
-        """Cholesky factor for the device mode (None clears), with_corr...py:339-341."""
+        """Cholesky factor [nb, nb] for the device mode and pde_residual (None
+        clears), with_corr...py:339-341.  Heston: nb = k, between the assets."""
         if L is None:
             _lib.check(self.lib.dbsde_set_corr(self.ctx, None, 0), self.ctx)
             return

@@ -162,7 +162,15 @@ int dbsde_brownian_dim(const dbsde_ctx* ctx);
  * the context keeps a device copy (n <= 128: held in registers by the path
  * kernel; above: streamed by the triangular increment GEMM).  L ==
  * NULL clears it.  Parity-mode batches (W != NULL) already carry correlated W
- * and ignore L.  DIAG problems only.
+ * and ignore L.
+ * Heston contexts: n = dbsde_brownian_dim = k = D / 2 <= 511 and L correlates
+ * the k assets' Brownian motions (each still drives its own S_i and v_i).  The
+ * device-mode rollout, dbsde_prefetch, dbsde_brownian and the rank shards
+ * (path0) then run on dW = L (sqrt(dt) z) -- the increment GEMM at every k,
+ * followed by a per-(path, asset) Euler chain -- and dbsde_pde_residual takes
+ * the columns of Sigma(x) . L.  dbsde_mc_value does not: it refuses a Heston
+ * problem with a factor.
+ * Any other n is DBSDE_EINVAL.
  */
 int dbsde_set_corr(dbsde_ctx* ctx, const float* L, int n);
 
@@ -288,7 +296,8 @@ int dbsde_net_u_jet(dbsde_ctx* ctx, const float* params, int R, const float* t, 
  *   diffusion  1/2 sum_j a_j^T D^2u a_j over the columns a_j of the diffusion matrix: DIAG
  *              diag(sig_a X + sig_b) . L (L: dbsde_set_corr, else I); Heston Sigma_i . (1, 1)^T
  *              per asset in its (S_i, v_i) plane, with the rollout's sqrt(max(v, 1e-8)) and
- *              +-100 clamps
+ *              +-100 clamps; with a factor between the assets (dbsde_set_corr, L [k, k])
+ *              column j of Sigma(x) . L: those entries of every asset i >= j times L[i][j]
  *   phi        phi_r (u - phi_c X . Du) + phi_zz |Du|^2   (q3 is ignored)
  *   residual   u_t + drift + diffusion - phi
  *   scale      |u_t| + |drift| + 1/2 sum_j |a_j^T D^2u a_j| + |phi|: what the residual is
