@@ -154,7 +154,7 @@ namespace {
 // ---------------------------------------------------------------------------
 int build_net(dbsde_ctx* c) {
   const dbsde_config& g = c->cfg;
-  if (g.n_layers < 4 || g.n_layers > 16) return fail(c, DBSDE_EINVAL, "len(layers) must be in [4, 16]");
+  if (g.n_layers < 4 || g.n_layers > 9) return fail(c, DBSDE_EINVAL, "len(layers) must be in [4, 9]");
   c->L.assign(g.layers, g.layers + g.n_layers);
   for (int v : c->L)
     if (v <= 0) return fail(c, DBSDE_EINVAL, "layer widths must be positive");
@@ -162,8 +162,7 @@ int build_net(dbsde_ctx* c) {
   c->D = c->L[0] - 1;
   if (c->L.back() != 1) return fail(c, DBSDE_EINVAL, "last layer width must be 1 (u is a scalar)");
   if (c->D < 1) return fail(c, DBSDE_EINVAL, "layers[0] must be D+1 >= 2");
-  c->K = n - 3;
-  if (c->K > 6) return fail(c, DBSDE_EINVAL, "at most 6 hidden blocks (len(layers) <= 9) are supported");
+  c->K = n - 3;   // 1..6 hidden blocks
   c->mode = g.mode;
   c->act = g.activation;
   if (c->act < 0 || c->act > 2) return fail(c, DBSDE_EINVAL, "unknown activation");

@@ -62,6 +62,31 @@ def test_abi_version_and_config_validation(lib):
     assert lib.dbsde_param_count(None) == -1
 
 
+def test_depth_limits_are_refused_with_the_limit_in_the_message(lib):
+    """len(layers) is 4..9 (include/dbsde.h), for Naisnet 4..6: one more is
+    EINVAL before any HIP call, and the message states the limit."""
+    pkg = load_pkg()
+    ctx = ctypes.c_void_p()
+
+    def create(mode, layers):
+        cfg = pkg._lib.Config()
+        cfg.mode, cfg.activation, cfg.n_layers = pkg._lib.MODES[mode], 0, len(layers)
+        for k, v in enumerate(layers):
+            cfg.layers[k] = v
+        rc = lib.dbsde_create(ctypes.byref(cfg), ctypes.byref(ctx))
+        return rc, lib.dbsde_last_error(None)
+
+    for mode in ("FC", "Resnet", "NAIS-Net", "Naisnet"):
+        rc, msg = create(mode, [5] + 8 * [16] + [1])            # len(layers) == 10
+        assert rc == pkg._lib.DBSDE_EINVAL and not ctx.value, mode
+        assert b"len(layers)" in msg and b"[4, 9]" in msg, msg
+    rc, msg = create("FC", [5, 16, 1])                          # len(layers) == 3
+    assert rc == pkg._lib.DBSDE_EINVAL and b"[4, 9]" in msg, msg
+    rc, msg = create("Naisnet", [5] + 5 * [16] + [1])           # len(layers) == 7
+    assert rc == pkg._lib.DBSDE_EINVAL and not ctx.value
+    assert b"Naisnet" in msg and b"{4,5,6}" in msg, msg
+
+
 C_PROBE = r'''
 #include <stdio.h>
 #include <stddef.h>

@@ -334,9 +334,12 @@ LAYOUTS = {
     "Naisnet-16-K3": ("Naisnet", [5, 16, 16, 16, 16, 1]),
     "NAIS-Net-16-K1": ("NAIS-Net", [5, 16, 16, 1]),
     "NAIS-Net-110-K3": ("NAIS-Net", [101, 110, 110, 110, 110, 1]),
+    "NAIS-Net-16-K5": ("NAIS-Net", [5] + 6 * [16] + [1]),         # the finalize table at P = 12 problem tiles
+    "NAIS-Net-110-K1": ("NAIS-Net", [101, 110, 110, 1]),          # 7-block tiles at P = 4
 }
 FUSED_CASES = [("NAIS-Net-16-K3", k) for k in R.KINDS] + \
-    [(lay, k) for lay in ("Naisnet-16-K3", "NAIS-Net-16-K1", "NAIS-Net-110-K3") for k in ("Adam", "Adadelta", "ASGD")]
+    [(lay, k) for lay in ("Naisnet-16-K3", "NAIS-Net-16-K1", "NAIS-Net-110-K3", "NAIS-Net-16-K5", "NAIS-Net-110-K1")
+     for k in ("Adam", "Adadelta", "ASGD")]
 
 
 @pytest.fixture(scope="module")
