@@ -13,9 +13,10 @@ Import it with importlib (the directory name is not a Python identifier):
 from . import _lib
 from .deepbsde import BlackScholesBarenblatt, u_exact
 from .fbsnn import FBSNN, PredictionGenerator
-from .problems import BasketCallOption, BSPDETestCase, CallOption, CallOption1D, HamiltonJacobiBellman, HestonFBSNN
+from .problems import (BasketCallOption, BSPDETestCase, CallOption, CallOption1D, HamiltonJacobiBellman, HestonFBSNN,
+                       HestonTwoFactorFBSNN)
 from .solver import NativeSolver, ProblemSpec, exact, hjb_mc, mc_value
 
 __all__ = ["FBSNN", "PredictionGenerator", "BlackScholesBarenblatt", "u_exact", "CallOption", "CallOption1D",
-           "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman", "HestonFBSNN", "NativeSolver",
-           "ProblemSpec", "exact", "hjb_mc", "mc_value", "_lib"]
+           "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman", "HestonFBSNN", "HestonTwoFactorFBSNN",
+           "NativeSolver", "ProblemSpec", "exact", "hjb_mc", "mc_value", "_lib"]

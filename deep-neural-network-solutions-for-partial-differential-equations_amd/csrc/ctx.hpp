@@ -125,9 +125,11 @@ struct dbsde_ctx {
 
   // ---- network description
   int mode = 0, act = 0, K = 0, D = 0;
-  int nb = 0;                 // Brownian dimension (D; D/2 for Heston)
+  int nb = 0;                 // Brownian dimension (D; D/2 for Heston, kind 1)
   int gcols = 0;              // state columns entering g and the terminal Z loss
   bool heston = false, u_clamp = false;
+  bool heston2 = false;       // DBSDE_PROB_HESTON2: two Brownian motions per asset (nb = D)
+  float rhob = 0.f;           // its fp32(sqrt(1 - (double)h_rho^2))
   float* Lt = nullptr;        // correlated device mode: L^T [nb][nb] (dbsde_set_corr)
   std::vector<int> L;
   bool has_v = false, proj = false;

@@ -1,7 +1,8 @@
 // evals.hip -- the references' exact / comparator solutions on the device:
 // the closed forms the drivers compare the learned Y against
 // (DeepBSDE.py:345-349, nd_BSPDE_case.py:587-658, with_corr...py:621-700) and
-// the HJB Monte-Carlo value (hjb_implement.py:1088-1095).  Exported through
+// the HJB Monte-Carlo value (hjb_implement.py:1088-1095), and the Heston
+// characteristic-function price of the two-factor model.  Exported through
 // include/dbsde.h (dbsde_exact, dbsde_hjb_mc); no context needed.
 #include <hip/hip_runtime.h>
 
@@ -31,7 +32,7 @@ __device__ __forceinline__ void bs_call(double S, double K, double tau, double r
 struct ExactArgs {
   int kind, D;
   long long R;
-  double T, p0, p1, p2;
+  double T, p0, p1, p2, p3, p4, p5;
   const float* t;
   const float* x;
   float* price;
@@ -69,6 +70,146 @@ __global__ void __launch_bounds__(256) exact_kernel(ExactArgs a) {
   }
   a.price[i] = (float)price;
   if (a.delta) a.delta[i] = (float)delta;
+}
+
+// --------------------------------------------------------------------------
+// DBSDE_EXACT_HESTON: the European call under the two-factor Heston model
+//   dS = r S dt + sqrt(v) S dW^S,  dv = kappa (theta - v) dt + sigma sqrt(v) dW^v,
+//   d<W^S, W^v> = rho dt        (DBSDE_PROB_HESTON2 with k = 1, mu_a = phi_r = r)
+// C = S P1 - K exp(-r tau) P2, delta = P1 (Heston 1993),
+//   P_j = 1/2 + 1/pi int_0^inf Re[exp(-i phi ln K) f_j(phi) / (i phi)] dphi,
+// f_j = exp(C_j + D_j v + i phi ln S) in the branch-stable form (Albrecher,
+// Mayer, Schoutens, Tistaert, "The little Heston trap", 2007): with u_1 = 1/2,
+// u_2 = -1/2, b_1 = kappa - rho sigma, b_2 = kappa, beta = b_j - rho sigma i phi,
+//   d = sqrt(beta^2 + sigma^2 (phi^2 - 2 u_j i phi))     (principal root, Re d >= 0)
+//   g = (beta - d) / (beta + d),  e = exp(-d tau)
+//   D = (beta - d) / sigma^2 (1 - e) / (1 - g e)
+//   C = r i phi tau + kappa theta / sigma^2 [(beta - d) tau - 2 (log(1 - g e) - log(1 - g))]
+// |g| < 1 and |e| <= 1, so both logarithms stay on the principal branch for
+// every phi and tau.  With E = C + D v + i phi ln(S / K) the integrand is
+// exp(Re E) sin(Im E) / phi.  fp64 throughout, own complex arithmetic.
+// Quadrature (include/dbsde.h): [0, U] in 64 equal panels, 8-point
+// Gauss-Legendre on each.  One wavefront per point, lane l owns panel l and
+// adds its 8 nodes in order; the 64 panel sums are added by a fixed xor
+// butterfly, so the result is bitwise repeatable.  U = 8 / sqrt(Vbar) times
+// the first power of sqrt(2) (at most 2^8) with exp(Re E_j(U)) <= 1e-10 U for
+// j = 1, 2: every lane runs that search on the same numbers.
+// --------------------------------------------------------------------------
+struct cplx {
+  double re, im;
+};
+__device__ __forceinline__ cplx operator+(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ cplx operator-(cplx a, cplx b) { return {a.re - b.re, a.im - b.im}; }
+__device__ __forceinline__ cplx operator*(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__device__ __forceinline__ cplx operator*(double s, cplx a) { return {s * a.re, s * a.im}; }
+__device__ __forceinline__ cplx operator/(cplx a, cplx b) {
+  const double q = 1.0 / (b.re * b.re + b.im * b.im);
+  return {(a.re * b.re + a.im * b.im) * q, (a.im * b.re - a.re * b.im) * q};
+}
+__device__ __forceinline__ cplx c_exp(cplx a) {
+  const double m = exp(a.re);
+  double sn, cs;
+  sincos(a.im, &sn, &cs);
+  return {m * cs, m * sn};
+}
+__device__ __forceinline__ cplx c_log(cplx a) { return {log(hypot(a.re, a.im)), atan2(a.im, a.re)}; }
+// principal square root (Re >= 0)
+__device__ __forceinline__ cplx c_sqrt(cplx a) {
+  const double m = hypot(a.re, a.im);
+  if (m == 0.0) return {0.0, 0.0};
+  if (a.re >= 0.0) {
+    const double t = sqrt(0.5 * (m + a.re));
+    return {t, 0.5 * a.im / t};
+  }
+  const double t = sqrt(0.5 * (m - a.re));
+  return {0.5 * fabs(a.im) / t, a.im >= 0.0 ? t : -t};
+}
+
+struct HestonCf {
+  double r, kappa, theta, sigma, rho, tau, v, x;   // x = ln(S / K)
+};
+// E_j(phi) = C_j + D_j v + i phi x
+__device__ __forceinline__ cplx heston_exponent(const HestonCf& h, int j, double phi) {
+  const double u = j == 1 ? 0.5 : -0.5;
+  const double b = j == 1 ? h.kappa - h.rho * h.sigma : h.kappa;
+  const double s2 = h.sigma * h.sigma;
+  const cplx one = {1.0, 0.0};
+  const cplx beta = {b, -h.rho * h.sigma * phi};
+  const cplx d = c_sqrt(beta * beta + cplx{s2 * phi * phi, -2.0 * u * s2 * phi});
+  const cplx bmd = beta - d;
+  const cplx g = bmd / (beta + d);
+  const cplx e = c_exp(-h.tau * d);
+  const cplx ge = one - g * e;
+  const cplx Dv = (1.0 / s2) * (bmd * ((one - e) / ge));
+  const cplx Cv = (h.kappa * h.theta / s2) * (h.tau * bmd - 2.0 * (c_log(ge) - c_log(one - g)));
+  const cplx E = Cv + h.v * Dv;
+  return {E.re, E.im + phi * (h.r * h.tau + h.x)};
+}
+
+constexpr int HQ_PANELS = 64;   // one per lane
+constexpr int HQ_GL = 8;
+__constant__ double HQ_X[HQ_GL] = {-0.9602898564975363, -0.7966664774136267, -0.5255324099163290, -0.1834346424956498,
+                                   0.1834346424956498,  0.5255324099163290,  0.7966664774136267,  0.9602898564975363};
+__constant__ double HQ_W[HQ_GL] = {0.1012285362903763, 0.2223810344533745, 0.3137066458778873, 0.3626837833783620,
+                                   0.3626837833783620, 0.3137066458778873, 0.2223810344533745, 0.1012285362903763};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// p0..p5 = r, K, kappa, theta, sigma, rho; x [R, 2] = (S, v)
+__global__ void __launch_bounds__(256) heston_call_kernel(ExactArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long r = blockIdx.x * 4LL + (threadIdx.x >> 6);
+  if (r >= a.R) return;   // whole waves leave together
+  const double S = (double)a.x[2 * r], v = (double)a.x[2 * r + 1], K = a.p1;
+  const double tau = a.T - (double)a.t[r];
+  double price, delta;
+  if (tau > 0.0) {
+    HestonCf h;
+    h.r = a.p0;
+    h.kappa = a.p2;
+    h.theta = a.p3;
+    h.sigma = a.p4;
+    h.rho = a.p5;
+    h.tau = tau;
+    h.v = v;
+    h.x = log(S / K);
+    // expected integrated variance: the scale of the integrand's decay
+    double vbar = h.theta * tau + (v - h.theta) * (1.0 - exp(-h.kappa * tau)) / h.kappa;
+    vbar = vbar > 1e-12 ? vbar : 1e-12;
+    double U = 8.0 / sqrt(vbar);
+    for (int it = 0; it < 16; ++it) {
+      const double m1 = exp(heston_exponent(h, 1, U).re), m2 = exp(heston_exponent(h, 2, U).re);
+      if ((m1 > m2 ? m1 : m2) <= 1e-10 * U) break;
+      U *= 1.4142135623730951;
+    }
+    const double hw = U / HQ_PANELS, mid = (lane + 0.5) * hw;
+    double s1 = 0.0, s2 = 0.0;
+    // not unrolled: sixteen inlined fp64 complex exponents at once take every
+    // register of the wave (256 VGPRs + 234 AGPRs, spilled SGPRs)
+#pragma unroll 1
+    for (int q = 0; q < HQ_GL; ++q) {
+      const double phi = mid + 0.5 * hw * HQ_X[q];
+      const cplx e1 = heston_exponent(h, 1, phi), e2 = heston_exponent(h, 2, phi);
+      s1 += HQ_W[q] * (exp(e1.re) * sin(e1.im) / phi);
+      s2 += HQ_W[q] * (exp(e2.re) * sin(e2.im) / phi);
+    }
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    const double P1 = 0.5 + 0.5 * hw * s1 * 0.31830988618379067154;
+    const double P2 = 0.5 + 0.5 * hw * s2 * 0.31830988618379067154;
+    price = S * P1 - K * exp(-h.r * tau) * P2;
+    delta = P1;
+  } else {
+    price = S - K > 0.0 ? S - K : 0.0;
+    delta = S > K ? 1.0 : (S == K ? 0.5 : 0.0);
+  }
+  if (lane != 0) return;
+  a.price[r] = (float)price;
+  if (a.delta) a.delta[r] = (float)delta;
 }
 
 // HJB Monte-Carlo: block (p, c) sums exp(-g(x_p + s_p z_k)) = 1 / (1/2 + |y|^2/2)
@@ -130,8 +271,9 @@ extern "C" {
 
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* stream) {
-  if (kind < DBSDE_EXACT_BSB || kind > DBSDE_EXACT_BASKET_MEAN || !t || !x || !params || !price || R < 1 || D < 1)
+  if (kind < DBSDE_EXACT_BSB || kind > DBSDE_EXACT_HESTON || !t || !x || !params || !price || R < 1 || D < 1)
     return DBSDE_EINVAL;
+  if (kind == DBSDE_EXACT_HESTON && D != 2) return DBSDE_EINVAL;   // x = (S, v): one asset
   ExactArgs a{};
   a.kind = kind;
   a.D = D;
@@ -144,6 +286,14 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
   a.x = x;
   a.price = price;
   a.delta = delta;
+  if (kind == DBSDE_EXACT_HESTON) {   // params = {r, K, kappa, theta, sigma, rho}; one wavefront per point
+    a.p3 = params[3];
+    a.p4 = params[4];
+    a.p5 = params[5];
+    if ((R + 3) / 4 > 0x7fffffffLL) return DBSDE_EINVAL;
+    heston_call_kernel<<<(unsigned)((R + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
+    return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
+  }
   const long long n = kind == DBSDE_EXACT_BS_CALL ? R * D : R;
   exact_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
   return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;

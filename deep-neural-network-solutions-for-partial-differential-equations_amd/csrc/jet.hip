@@ -333,8 +333,9 @@ int launch_tw(const JetArgs& a, int point, hipStream_t s) {
 // ---------------------------------------------------------------------------
 struct PdeArgs {
   dbsde_problem pr;
-  int heston, D, nb, nd;
-  const float* Lt;       // [nb][nb] L^T (dbsde_set_corr) or null
+  int heston, D, nb, nd;   // heston: 0 DIAG, 1 HESTON, 2 HESTON2
+  float rhob;              // HESTON2: fp32(sqrt(1 - (double)h_rho^2))
+  const float* Lt;      // [nb][nb] L^T (dbsde_set_corr) or null
   const float* X;
   long long r0;          // the chunk's first point
   int np;                // points of the chunk
@@ -352,7 +353,8 @@ __device__ __forceinline__ float clamp100(float x) { return fminf(fmaxf(x, -100.
 // DIAG diag(sig_a X + sig_b) . L; Heston Sigma_j . (1, 1)^T in the (S_j, v_j)
 // plane with the rollout's sqrt(max(v, 1e-8)) and +-100 clamps (paths.hpp),
 // and with a factor L between the assets column j of Sigma(x) . L: for every
-// asset i >= j the (S_i, v_i) entries of Sigma_i . (1, 1)^T times L[i][j]
+// asset i >= j the (S_i, v_i) entries of Sigma_i . (1, 1)^T times L[i][j];
+// two-factor Heston (nd = 1 + 2k) the 2k columns of its diffusion matrix
 __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
   const int ld = a.D + 1;
   const long long n = (long long)a.np * a.nd * ld;
@@ -368,7 +370,18 @@ __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
     v = c == 0 ? 1.f : 0.f;
   } else if (c > 0) {
     const int jb = j - 1, d = c - 1;
-    if (a.heston) {
+    if (a.heston == 2) {
+      // two-factor Heston, k = D / 2: direction 1 + i is the dW^S_i column
+      // (S_i: d00, v_i: d10), direction 1 + k + i the dW^v_i column (v_i: d11)
+      const int k = a.D >> 1;
+      const int i = d < k ? d : d - k;   // the asset of column d
+      if (i == (jb < k ? jb : jb - k) && (jb < k || d >= k)) {
+        const float S = x[i], vv = x[k + i];
+        const float sv = sqrtf(fmaxf(vv, 1e-8f));
+        const float sigV = a.pr.h_sigma * sv;
+        v = jb >= k ? clamp100(a.rhob * sigV) : (d < k ? clamp100(sv * S) : clamp100(a.pr.h_rho * sigV));
+      }
+    } else if (a.heston) {
       const int k = a.nb;
       const int i = d < k ? d : d - k;   // the asset of column d
       if (a.Lt ? i >= jb : i == jb) {
@@ -402,7 +415,7 @@ __global__ void __launch_bounds__(256) pde_terms_kernel(PdeArgs a) {
   const float* x = a.X + (size_t)p * D;
   const float* du = a.Du + (size_t)p * D;
   float drift = 0.f, xz = 0.f, zz = 0.f;
-  const int k = a.nb;
+  const int k = a.heston == 2 ? D >> 1 : a.nb;   // assets of a Heston state
   for (int d = lane; d < D; d += 64) {
     const float xd = x[d], zd = du[d];
     float mu;
@@ -663,7 +676,8 @@ int dbsde_pde_residual(dbsde_ctx* c, const float* params, int R, const float* t,
     PdeArgs pa;
     memset(&pa, 0, sizeof(pa));
     pa.pr = c->cfg.problem;
-    pa.heston = c->heston ? 1 : 0;
+    pa.heston = c->heston2 ? 2 : (c->heston ? 1 : 0);
+    pa.rhob = c->rhob;
     pa.D = D;
     pa.nb = c->nb;
     pa.nd = nd;

@@ -12,7 +12,11 @@
 // mu_eff = mu_a + phi_r phi_c (fp32, computed once).  Check: BSB has mu = 0,
 // sigma = 0.4 X, phi = r (Y - X.Z): exp((r + sigma^2) tau) |x|^2 = DBSDE_EXACT_BSB.
 // Heston has phi_c = 0 and its own drift and 2x2 blocks, stepped exactly as
-// rollout_heston_kernel steps them.  phi_zz != 0 (HJB) is not linear: dbsde_hjb_mc.
+// rollout_heston_kernel steps them; the two-factor Heston (DBSDE_PROB_HESTON2,
+// path kind MC_HESTON2) runs heston2_step (rn.hpp) on two normals per step,
+// those of coordinates d (W^S_d) and nd + d (W^v_d), nd = D / 2 -- the
+// increments rollout_heston2_kernel draws.  phi_zz != 0 (HJB) is not linear:
+// dbsde_hjb_mc.
 //
 // Draws.  The normals of sample k, step n, Brownian coordinate d are
 // philox_normal4(seed, offset, k, n >> 2, d)[n & 3] -- the device-mode rollout's
@@ -50,6 +54,7 @@
 // Nothing per path goes to HBM.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <string>
 
 #include "../../include/dbsde.h"
@@ -69,7 +74,7 @@ constexpr int MC_DMAX = 4096;
 constexpr int MC_NBMAX = 128;      // correlated: L in LDS
 constexpr int MC_LPACK = MC_NBMAX * (MC_NBMAX + 1) / 2;
 constexpr int MC_ZMAX = 2048;       // correlated: floats of the Z (and C) tile, nd x (4 S padded to 16) <= 2048
-enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2 };
+enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2, MC_HESTON2 = 3 };
 
 typedef float mcf4 __attribute__((ext_vector_type(4)));
 
@@ -80,6 +85,7 @@ struct McArgs {
   float strike, g_alpha, phi_r, T;
   float mu, sig_a, sig_b;          // DIAG: mu = mu_eff
   float kappa, theta, hsig, rho;   // Heston (mu = mu_a)
+  float rhob;                      // two-factor Heston: fp32(sqrt(1 - (double)rho^2))
   long long mc, per;               // samples, samples per chunk
   unsigned long long seed, offset;
   const float* t;                  // [P]
@@ -146,7 +152,7 @@ __device__ __forceinline__ void mc_payoff(int g_kind, double s, double cols, dou
 }
 
 // The whole path of sample k, thread coordinate d, for the tile's MC_PT
-// points.  DIAG / CORR: X the state, V the tangent J (DELTA).  HESTON: X = S_d,
+// points.  DIAG / CORR: X the state, V the tangent J (DELTA).  HESTON / HESTON2: X = S_d,
 // V = v_d.  s: the thread's sample slot, act: the thread owns a (sample,
 // coordinate) pair.  Every thread of the workgroup calls this (CORR has
 // barriers inside).
@@ -157,6 +163,8 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
   for (int n0 = 0; n0 < a.n_steps; n0 += 4) {
     float z[4];
     philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)d, z);
+    float zv[4] = {0.f, 0.f, 0.f, 0.f};   // two-factor Heston: the normals of W^v_d, coordinate nd + d
+    if constexpr (KIND == MC_HESTON2) philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)(a.nd + d), zv);
     if constexpr (KIND == MC_CORR) {
       // dW^T = L . Z on the matrix cores.  Z [nd][NCp]: row j = coordinate, column
       // 4 s + i = step i of sample slot s (NCp = the 4 S columns padded to 16).
@@ -214,7 +222,10 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
       for (int i = 0; i < MC_PT; ++i) {
         const float dt = dtr[i];
         const float w = rn_mul(sq[i], z[kk]);
-        if constexpr (KIND == MC_HESTON) {
+        if constexpr (KIND == MC_HESTON2) {
+          float sa, sb;
+          heston2_step(a.mu, a.kappa, a.theta, a.hsig, a.rho, a.rhob, dt, w, rn_mul(sq[i], zv[kk]), X[i], V[i], sa, sb);
+        } else if constexpr (KIND == MC_HESTON) {
           const float S = X[i], v = V[i];
           const float muS = clamp100(rn_mul(a.mu, S));
           const float muV = clamp100(rn_mul(a.kappa, rn_sub(a.theta, v)));
@@ -288,14 +299,14 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
 #pragma unroll
       for (int i = 0; i < MC_PT; ++i) {
         X[i] = a.x[(size_t)pc[i] * a.D + dd];
-        V[i] = KIND == MC_HESTON ? a.x[(size_t)pc[i] * a.D + nd + dd] : 1.f;
+        V[i] = (KIND == MC_HESTON || KIND == MC_HESTON2) ? a.x[(size_t)pc[i] * a.D + nd + dd] : 1.f;
       }
       mc_path<KIND, DELTA>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls);
       if (dl) {
 #pragma unroll
         for (int i = 0; i < MC_PT; ++i) {
           if (dd < a.gcols) fs[i] += squares ? (double)X[i] * (double)X[i] : (double)X[i];
-          if (KIND == MC_HESTON && nd + dd < a.gcols)
+          if ((KIND == MC_HESTON || KIND == MC_HESTON2) && nd + dd < a.gcols)
             fs[i] += squares ? (double)V[i] * (double)V[i] : (double)V[i];
         }
       }
@@ -436,11 +447,13 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (P < 1 || D < 1 || n_steps < 1 || mc < 1) return bad("P, D, n_steps and mc must be >= 1");
   if (mc > (1LL << 32)) return bad("mc must be <= 2^32 (the sample index is a 32-bit counter word)");
   if (D > MC_DMAX) return bad("D must be <= 4096");
-  if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON) return bad("unknown problem kind");
+  if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2)
+    return bad("unknown problem kind");
   if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_CALL) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
     return bad("phi_zz != 0 is not a linear problem (no Feynman-Kac expectation); the HJB comparator is dbsde_hjb_mc");
-  const bool heston = prob->kind == DBSDE_PROB_HESTON;
+  const bool heston2 = prob->kind == DBSDE_PROB_HESTON2;   // the same state and the same refusals
+  const bool heston = prob->kind == DBSDE_PROB_HESTON || heston2;
   if (heston && (D & 1)) return bad("the Heston state [S_1..S_k, v_1..v_k] needs an even D");
   if (heston && L) return bad("L applies to DIAG problems only");
   if (heston && delta)
@@ -474,6 +487,8 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   a.theta = prob->h_theta;
   a.hsig = prob->h_sigma;
   a.rho = prob->h_rho;
+  if (heston2 && !(std::fabs((double)prob->h_rho) <= 1.0)) return bad("two-factor Heston needs |h_rho| <= 1");
+  a.rhob = heston2 ? (float)std::sqrt(1.0 - (double)prob->h_rho * (double)prob->h_rho) : 0.f;
   a.mc = mc;
   a.seed = seed;
   a.offset = offset;
@@ -496,7 +511,9 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
 
   mc_grid_kernel<<<(a.Ppad + 255) / 256, 256, 0, st>>>(a);
   const dim3 grid(tiles, a.nch);
-  if (heston)
+  if (heston2)
+    mc_kernel<MC_HESTON2, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (heston)
     mc_kernel<MC_HESTON, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (L && delta)
     mc_kernel<MC_CORR, true><<<grid, MC_THREADS, 0, st>>>(a);

@@ -269,11 +269,17 @@ int build_net(dbsde_ctx* c) {
   c->x3chain = c->tnx3 && !c->fused;
   // problem kind: Brownian dimension, g columns, u clamp
   const dbsde_problem& pr = g.problem;
-  if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON) return fail(c, DBSDE_EINVAL, "unknown problem kind");
+  if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON && pr.kind != DBSDE_PROB_HESTON2)
+    return fail(c, DBSDE_EINVAL, "unknown problem kind");
   if (pr.g_kind < 0 || pr.g_kind > 4) return fail(c, DBSDE_EINVAL, "unknown terminal condition");
   c->heston = pr.kind == DBSDE_PROB_HESTON;
-  if (c->heston && c->D % 2 != 0)
+  c->heston2 = pr.kind == DBSDE_PROB_HESTON2;
+  if ((c->heston || c->heston2) && c->D % 2 != 0)
     return fail(c, DBSDE_EINVAL, "Heston state is [S_1..S_k, v_1..v_k]: layers[0] - 1 must be even");
+  // two-factor Heston: |rho| <= 1, and the v-column weight of the second Brownian motion
+  if (c->heston2 && !(std::fabs((double)pr.h_rho) <= 1.0))
+    return fail(c, DBSDE_EINVAL, "two-factor Heston needs |h_rho| <= 1");
+  c->rhob = c->heston2 ? (float)std::sqrt(1.0 - (double)pr.h_rho * (double)pr.h_rho) : 0.f;
   c->nb = c->heston ? c->D / 2 : c->D;
   c->gcols = pr.g_cols > 0 ? pr.g_cols : c->D;
   if (c->gcols > c->D) return fail(c, DBSDE_EINVAL, "g_cols exceeds the state dimension");

@@ -40,6 +40,7 @@ struct RolloutArgs {
   long long path0;
   float mu_a, sig_a, sig_b;                // diagonal problems
   float kappa, theta, hsig, rho;           // Heston
+  float rhob;                              // two-factor Heston: fp32(sqrt(1 - (double)rho^2))
   const float* Lt;       // correlated device mode: L^T [nb][nb] (upper part of L^T zero)
   float* xin;            // [Rp, ldx]
   float* sdw;            // [Rp, ldx]
@@ -985,6 +986,88 @@ __global__ void __launch_bounds__(256) rollout_heston_chain_kernel(RolloutArgs p
   xr[1 + k + i] = v;
   sr[1 + i] = 0.0f;
   sr[1 + k + i] = 0.0f;
+  if (i == 0) {
+    xr[0] = t0;
+    xr[p.D + 1] = 1.0f;
+  }
+}
+
+// --------------------------------------------------------------------------
+// Two-factor Heston (DBSDE_PROB_HESTON2): the textbook model, two Brownian
+// motions per asset.  State [S_1..S_k, v_1..v_k], Brownian dimension nb = 2k:
+// coordinate i is W^S_i, coordinate k + i is W^v_i, all independent.  Thread
+// per (path m, asset i), sequential over n; per 4-step Philox block it draws
+// coordinates i and k + i with the diagonal rollout's key (seed, offset, global
+// path, step block, coordinate), so the increments are those of a diagonal
+// problem with D = 2k.  The step, every operation rounded on its own (rn_*,
+// correctly rounded sqrt, c = clamp100), w1 / w2 the increments of W^S_i / W^v_i:
+//   sv  = sqrt(max(v, 1e-8))
+//   muS = c(mu_a S)          muV = c(kappa (theta - v))
+//   d00 = c(sv S)            d10 = c(rho (sig sv))         d11 = c(rhob (sig sv))
+//   a   = d00 w1             b   = d10 w1 + d11 w2         (the sdw columns S_i, v_i)
+//   S1  = (S + muS dt) + a   v1  = (v + muV dt) + b
+// rhob = fp32(sqrt(1 - (double)rho^2)) comes from the host.  One kernel serves
+// the rollout (device grid or the caller's t / W [M, N+1, 2k]) and the two
+// fetch outputs.  A wave's 64 threads store two runs of up to 256 contiguous
+// bytes per row and array, as rollout_heston_kernel does.
+// --------------------------------------------------------------------------
+// The step itself is heston2_step (rn.hpp), shared with the Monte-Carlo comparator.
+constexpr int H2_THREADS = 256;
+__global__ void __launch_bounds__(H2_THREADS) rollout_heston2_kernel(RolloutArgs p) {
+  const int k = p.D >> 1;   // nb = D = 2k
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= p.M * k) return;
+  const int m = gid / k, i = gid - m * k;
+  const int N1 = p.N + 1;
+  const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
+  float S = xi[i], v = xi[k + i];
+  const double dt64 = (double)p.T / (double)p.N;
+  const float sqdt = sqrtf(p.T / (float)p.N);
+  double tacc = 0.0;
+  float t0 = p.t ? p.t[(size_t)m * N1] : 0.0f;
+  float w0s = p.W ? p.W[(size_t)m * N1 * p.nb + i] : 0.0f;
+  float w0v = p.W ? p.W[(size_t)m * N1 * p.nb + k + i] : 0.0f;
+  size_t r = (size_t)m * N1;
+  FetchAcc fs, fv;
+  if (p.out != PATH_ROLLOUT) {
+    fs.put(p, m, i, 0, t0, 0.f);
+    fv.put(p, m, k + i, 0, t0, 0.f);
+  }
+  for (int n0 = 0; n0 < p.N; n0 += 4) {
+    // both calls see the same grid sum, so t1 is the same from each
+    float dws[4], dwv[4], t1[4];
+    double tn = tacc;
+    step_block(p, m, i, n0, w0s, tn, dt64, sqdt, dws, t1);
+    step_block(p, m, k + i, n0, w0v, tacc, dt64, sqdt, dwv, t1);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      if (n0 + kk >= p.N) break;
+      if (p.out != PATH_ROLLOUT) {
+        fs.put(p, m, i, n0 + kk + 1, t1[kk], dws[kk]);
+        fv.put(p, m, k + i, n0 + kk + 1, t1[kk], dwv[kk]);
+        continue;
+      }
+      float* xr = p.xin + r * p.ldx;
+      xr[1 + i] = S;
+      xr[1 + k + i] = v;
+      if (i == 0) {
+        xr[0] = t0;
+        xr[p.D + 1] = 1.0f;
+      }
+      float a, b;
+      heston2_step(p.mu_a, p.kappa, p.theta, p.hsig, p.rho, p.rhob, rn_sub(t1[kk], t0), dws[kk], dwv[kk], S, v, a, b);
+      p.sdw[r * p.ldx + 1 + i] = a;
+      p.sdw[r * p.ldx + 1 + k + i] = b;
+      t0 = t1[kk];
+      ++r;
+    }
+  }
+  if (p.out != PATH_ROLLOUT) return;
+  float* xr = p.xin + r * p.ldx;   // n = N
+  xr[1 + i] = S;
+  xr[1 + k + i] = v;
+  p.sdw[r * p.ldx + 1 + i] = 0.0f;
+  p.sdw[r * p.ldx + 1 + k + i] = 0.0f;
   if (i == 0) {
     xr[0] = t0;
     xr[p.D + 1] = 1.0f;

@@ -6,6 +6,7 @@
 // above it the increment GEMM rollout_corrw_kernel followed by the Euler chains.
 // Correlated Heston (L between the k assets): the increment GEMM at every k,
 // then rollout_heston_chain_kernel.
+// Two-factor Heston (DBSDE_PROB_HESTON2): rollout_heston2_kernel for everything.
 #include <hip/hip_runtime.h>
 
 // a prefetched rollout runs on the next chunked step's second stream
@@ -71,6 +72,7 @@ RolloutArgs rollout_args(dbsde_ctx* c, const dbsde_batch* b, float* xin, float* 
   ra.theta = pr.h_theta;
   ra.hsig = pr.h_sigma;
   ra.rho = pr.h_rho;
+  ra.rhob = c->rhob;
   ra.Lt = c->Lt;
   ra.xin = xin;
   ra.sdw = sdw;
@@ -103,6 +105,17 @@ int heston_chain_threads() {
   return n;
 }
 
+// workgroup size of rollout_heston2_kernel: H2_THREADS; DBSDE_H2_THREADS = 64 or
+// 128 (read once) is the measurement switch of tools/heston2_profile.py
+int heston2_threads() {
+  static const int n = [] {
+    const char* e = getenv("DBSDE_H2_THREADS");
+    const int v = e ? atoi(e) : H2_THREADS;
+    return v == 64 || v == 128 ? v : H2_THREADS;
+  }();
+  return n;
+}
+
 // Euler-Maruyama paths (ra.out == PATH_ROLLOUT) or the device fetch_minibatch
 // (PATH_FETCH_*): Heston, Cholesky-correlated device mode, or diagonal
 // side: a prefetched rollout running beside other work (the two-pass form's
@@ -112,7 +125,14 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
   const char* name = ra.out == PATH_ROLLOUT ? "rollout" : "brownian";
   const double steps = (double)ra.M * ra.N;
   const double bytes = ra.out == PATH_ROLLOUT ? 4.0 * steps * (2.0 * ra.D + (ra.W ? ra.nb : 0)) : 4.0 * steps * ra.nb;
-  if (c->Lt && !ra.W && (c->heston || ra.nb > CP_NBMAX)) {
+  if (c->heston2) {
+    // two-factor Heston (never with a factor: dbsde_set_corr refuses it): one
+    // kernel for device- and parity-mode batches, in-step and prefetched, and
+    // for the fetch; thread per (path, asset)
+    if (ra.nb != ra.D || (ra.D & 1)) return fail(c, DBSDE_EINVAL, "internal: two-factor Heston rollout geometry");
+    const int nthr = ra.M * (ra.D / 2), ht = heston2_threads();
+    RUN(c, s, name, 0.0, bytes, rollout_heston2_kernel<<<(nthr + ht - 1) / ht, ht, 0, s>>>(ra));
+  } else if (c->Lt && !ra.W && (c->heston || ra.nb > CP_NBMAX)) {
     // wide correlated device mode, and correlated Heston at every k (paths.hpp):
     // the triangular GEMM dW = L (sqrt(dt) z) over (path group, step block),
     // then the Euler chains or the fetch sums
@@ -331,6 +351,10 @@ int dbsde_brownian_dim(const dbsde_ctx* c) { return c ? c->nb : -1; }
 
 int dbsde_set_corr(dbsde_ctx* c, const float* L, int n) {
   if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
+  if (c->heston2 && L)
+    return fail(c, DBSDE_EINVAL,
+                "dbsde_set_corr: the two-factor Heston problem takes no factor (correlation between assets is out "
+                "of scope for it)");
   HIPC(c, hipSetDevice(c->device));
   // a prefetched rollout read the old factor: drop it and let it finish (the
   // host waits for pf_stream here, and below, before the factor changes, for

@@ -11,10 +11,12 @@ methods (generic.py) instead of silently training the parent's problem.
   BSPDETestCase         with_corr...py:599-616          sum X^2 payoff, mu = 0.05 X
   HamiltonJacobiBellman hjb_implement.py:590-604        phi = |Z|^2, g = log(1/2 + |X|^2/2)
   HestonFBSNN           heston_dnnpde.py:519-699        k-asset stochastic volatility
+  HestonTwoFactorFBSNN  (no reference counterpart)      the two-factor Heston model on that surface
   BlackScholesBarenblatt: see deepbsde.py (DeepBSDE.py:326-341 surface)
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 
 import numpy as np
@@ -23,6 +25,7 @@ import torch
 from . import networks
 from .fbsnn import FBSNN
 from .solver import ProblemSpec
+from .solver import exact as _exact
 
 
 class CallOption(FBSNN):
@@ -301,5 +304,73 @@ class HestonFBSNN(FBSNN):
         return mid.float().cpu().numpy(), delta.cpu().numpy(), gamma.cpu().numpy()
 
 
+class HestonTwoFactorFBSNN(HestonFBSNN):
+    """The two-factor (textbook) Heston model on HestonFBSNN's surface.
+
+    HestonFBSNN follows the reference, whose FBSNN dimension is 1: one scalar
+    Brownian motion per asset drives both S_i and v_i, a degenerate one-factor
+    diffusion.  Here each asset has two Brownian motions W^S_i and W^v_i with
+    correlation rho between them (problem kind "heston2", include/dbsde.h
+    DBSDE_PROB_HESTON2), so the network solves
+
+      u_t + r S u_S + kappa (theta - v) u_v + 1/2 v S^2 u_SS + rho sigma v S u_Sv
+          + 1/2 sigma^2 v u_vv - r u = 0,   u(T, .) = g,   r = 0.05,
+
+    per asset.  State, network, payoffs, u clamp, NaN skip, predict,
+    calculate_greeks, mc_value and mc_greeks are HestonFBSNN's; the Brownian
+    dimension is 2k: column i of W is W^S_i, column k + i is W^v_i, all
+    independent (fetch_minibatch draws 2k columns).  Limits: no correlation
+    between assets (any correlation_type but "no_correlation" raises
+    ValueError), no pathwise Monte-Carlo delta (mc_greeks bumps and reprices),
+    and closed_form -- the characteristic-function price -- for one asset and
+    the call payoff only."""
+
+    def __init__(self, Xi, T, M, N, D, Mm, layers, mode, activation, correlation_type="no_correlation", **kw):
+        if correlation_type != "no_correlation":
+            raise ValueError("HestonTwoFactorFBSNN has no correlation between assets: correlation_type must be "
+                             "'no_correlation' (rho correlates each asset's own two Brownian motions)")
+        if not abs(kw.get("rho", 0.8)) <= 1.0:
+            raise ValueError("rho must lie in [-1, 1]")
+        super().__init__(Xi, T, M, N, D, Mm, layers, mode, activation, correlation_type, **kw)
+
+    def problem_spec(self):
+        return dataclasses.replace(super().problem_spec(), kind="heston2")
+
+    def sigma_tf(self, t, X, Y=None):
+        """The diffusion matrix [R, 2k, 2k] of the kind-2 step: column i (dW^S_i)
+        holds (S_i: sv S, v_i: rho sigma sv), column k + i (dW^v_i) holds
+        (v_i: sqrt(1 - rho^2) sigma sv), sv = sqrt(max(v, 1e-8)), every entry
+        clamped to [-100, 100]."""
+        k = self.n_assets
+        S, v = X[:, :k], X[:, k:]
+        sv = torch.sqrt(torch.clamp(v, min=1e-8))
+        sigV = self.sigma * sv
+        A = torch.zeros((X.shape[0], 2 * k, 2 * k), dtype=X.dtype, device=X.device)
+        i = torch.arange(k, device=X.device)
+        A[:, i, i] = (sv * S).clamp(-100, 100)
+        A[:, k + i, i] = (self.rho * sigV).clamp(-100, 100)
+        A[:, k + i, k + i] = (math.sqrt(1.0 - self.rho ** 2) * sigV).clamp(-100, 100)
+        return A
+
+    def closed_form(self, S, v, t):
+        """The Heston characteristic-function price of this object's problem at
+        the points (S [R], v [R], t [R]): (price [R, 1], delta [R, 1] = dprice/dS)
+        as float32 tensors on the device, through exact("heston", ...)
+        (DBSDE_EXACT_HESTON) with r = 0.05 and this object's strike, kappa,
+        theta, sigma and rho.  One asset and the call payoff ('discontinuous')
+        only: anything else raises ValueError."""
+        if self.n_assets != 1:
+            raise ValueError("closed_form exists for one asset only (k = 1)")
+        if self.payoff_type != "discontinuous":
+            raise ValueError("closed_form prices the call payoff ('discontinuous') only")
+        S = torch.as_tensor(np.asarray(S), dtype=torch.float32).to(self.device).reshape(-1)
+        v = torch.as_tensor(np.asarray(v), dtype=torch.float32).to(self.device).reshape(-1)
+        t = torch.as_tensor(np.asarray(t), dtype=torch.float32).to(self.device).reshape(-1)
+        if not (S.numel() == v.numel() == t.numel()):
+            raise ValueError("S, v and t must hold the same number of points")
+        return _exact("heston", t, torch.stack([S, v], dim=1).contiguous(), self.T,
+                      (0.05, self.strike, self.kappa, self.theta, self.sigma, self.rho))
+
+
 __all__ = ["CallOption", "CallOption1D", "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman",
-           "HestonFBSNN"]
+           "HestonFBSNN", "HestonTwoFactorFBSNN"]

@@ -20,6 +20,9 @@ class ProblemSpec:
     kind "diag":   mu = mu_a X, sigma = diag(sig_a X + sig_b)
     kind "heston": k-asset Heston (heston_dnnpde.py:587-605) with S-drift mu_a,
                    kappa/theta/sigma/rho, state [S_1..S_k, v_1..v_k]
+    kind "heston2": the two-factor (textbook) Heston model on the same state and
+                   fields: Brownian motions W^S_i, W^v_i per asset (nb = 2k)
+                   with correlation rho between the two, none between assets
     phi = phi_r (Y - phi_c X.Z) + phi_zz |Z|^2, g = g_kind(strike, alpha) over
     the first g_cols state columns (0 = all), u_clamp: u = max(net, 0).
     q3: reproduce the D == 1 squeeze broadcast."""
@@ -378,8 +381,10 @@ class NativeSolver:
 # ---------------------------------------------------------------------- evaluators
 def exact(kind, t, X, T, params):
     """Device exact / comparator solutions (include/dbsde.h dbsde_exact):
-    kind in {"bsb", "bs_call", "basket_avg", "basket_mean"}; t [R], X [R, D]
-    float32 cuda tensors.  Returns (price, delta); delta is None for "bsb"."""
+    kind in {"bsb", "bs_call", "basket_avg", "basket_mean", "heston"}; t [R],
+    X [R, D] float32 cuda tensors.  Returns (price, delta); delta is None for
+    "bsb".  "heston": the European call of the two-factor Heston model, X [R, 2]
+    = (S, v), params = (r, K, kappa, theta, sigma, rho), delta [R, 1] = dprice/dS."""
     lib = _lib.load()
     if kind not in _lib.EXACT_KINDS:
         raise ValueError(f"unknown exact solution {kind!r}")
@@ -392,7 +397,11 @@ def exact(kind, t, X, T, params):
     price = torch.empty((R, ncol), device=X.device)
     delta = None if kind == "bsb" else torch.empty((R, ncol), device=X.device)
     import numpy as np
-    p = np.zeros(3, dtype=np.float64)
+    p = np.zeros(6, dtype=np.float64)
+    if len(params) > (6 if kind == "heston" else 3):
+        raise ValueError(f"too many parameters for {kind!r}")
+    if kind == "heston" and len(params) != 6:
+        raise ValueError("'heston' takes params = (r, K, kappa, theta, sigma, rho)")
     p[:len(params)] = params
     s = torch.cuda.current_stream(X.device).cuda_stream
     _lib.check(lib.dbsde_exact(_lib.EXACT_KINDS[kind], _ptr(t), _ptr(X), R, D, float(T),

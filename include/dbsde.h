@@ -66,6 +66,9 @@ extern "C" {
 #define DBSDE_PROB_DIAG 0     /* mu = mu_a X, sigma = diag(sig_a X + sig_b)          */
 #define DBSDE_PROB_HESTON 1   /* k-asset Heston (heston_dnnpde.py:519-659), state
                                  [S_1..S_k, v_1..v_k], one Brownian motion per asset */
+#define DBSDE_PROB_HESTON2 2  /* the two-factor (textbook) Heston model, the same state:
+                                 Brownian motions W^S_i and W^v_i per asset, correlation
+                                 h_rho between the two, none between assets            */
 
 /*
  * Problem coefficients (one FBSNN subclass = one filled struct):
@@ -78,7 +81,23 @@ extern "C" {
  *     Sigma_i  = clamp([[sv S_i, h_rho h_sigma sv], [h_rho sv S_i, h_sigma sv]], -100, 100)
  *     driven by the asset's scalar dW_i (the reference's FBSNN dimension is 1;
  *     its einsum broadcasts dW over both state components)
- *   phi      = phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
+ *   kind HESTON2, the same fields, state and D = 2k (even, else DBSDE_EINVAL), but
+ *     the Brownian dimension is nb = D: column i of W is W^S_i, column k + i is
+ *     W^v_i, all 2k independent.  Per asset, with sv = sqrt(max(v, 1e-8)),
+ *     c(x) = clamp(x, -100, 100), rhob = fp32(sqrt(1 - (double)h_rho^2)) (host,
+ *     once; |h_rho| <= 1) and every operation rounded to fp32 on its own, in
+ *     this order (w1, w2 the increments of W^S_i and W^v_i):
+ *       muS = c(mu_a S)            muV = c(h_kappa (h_theta - v))
+ *       d00 = c(sv S)              d10 = c(h_rho (h_sigma sv))   d11 = c(rhob (h_sigma sv))
+ *       S1  = (S + muS dt) + d00 w1
+ *       v1  = (v + muV dt) + (d10 w1 + d11 w2)
+ *       sigma dW (the Y-tilde term): S_i: d00 w1,  v_i: d10 w1 + d11 w2
+ *     i.e. the PDE  u_t + mu_a S u_S + kappa (theta - v) u_v + 1/2 v S^2 u_SS
+ *     + rho sigma v S u_Sv + 1/2 sigma^2 v u_vv - phi_r u = 0 per asset.
+ *     dbsde_set_corr on such a context is DBSDE_EINVAL (no correlation between
+ *     assets), dbsde_mc_value takes neither L nor delta for it, and
+ *     DBSDE_EXACT_HESTON is its closed form for k = 1 and a call payoff.
+ *   phi      =phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
  *   g        = g_kind over the first g_cols state columns (0 = all), strike,
  *              g_alpha (DBSDE_G_SMOOTH_CALL); the terminal |Z - grad g|^2 term
  *              runs over the same columns (heston_dnnpde.py:654: dU/dS only)
@@ -152,7 +171,7 @@ int dbsde_param_used_mask(const dbsde_ctx* ctx, unsigned char* mask, long long n
  * create time (DBSDE_X3=0 / DBSDE_TNW_X3=0 select the fp32 forms). */
 int dbsde_matrix_form(const dbsde_ctx* ctx);
 
-/* Brownian dimension nb of a batch's W [M, N+1, nb]: D, or D/2 for Heston */
+/* Brownian dimension nb of a batch's W [M, N+1, nb]: D (DIAG, HESTON2), or D/2 for HESTON */
 int dbsde_brownian_dim(const dbsde_ctx* ctx);
 
 /*
@@ -170,6 +189,8 @@ int dbsde_brownian_dim(const dbsde_ctx* ctx);
  * followed by a per-(path, asset) Euler chain -- and dbsde_pde_residual takes
  * the columns of Sigma(x) . L.  dbsde_mc_value does not: it refuses a Heston
  * problem with a factor.
+ * HESTON2 contexts: DBSDE_EINVAL (correlation between assets is out of scope
+ * for the two-factor model; L == NULL is accepted and does nothing).
  * Any other n is DBSDE_EINVAL.
  */
 int dbsde_set_corr(dbsde_ctx* ctx, const float* L, int n);
@@ -297,7 +318,8 @@ int dbsde_net_u_jet(dbsde_ctx* ctx, const float* params, int R, const float* t, 
  *              diag(sig_a X + sig_b) . L (L: dbsde_set_corr, else I); Heston Sigma_i . (1, 1)^T
  *              per asset in its (S_i, v_i) plane, with the rollout's sqrt(max(v, 1e-8)) and
  *              +-100 clamps; with a factor between the assets (dbsde_set_corr, L [k, k])
- *              column j of Sigma(x) . L: those entries of every asset i >= j times L[i][j]
+ *              column j of Sigma(x) . L: those entries of every asset i >= j times L[i][j];
+ *              HESTON2 its 2k columns: dW^S_i -> (S_i: d00, v_i: d10), dW^v_i -> (v_i: d11)
  *   phi        phi_r (u - phi_c X . Du) + phi_zz |Du|^2   (q3 is ignored)
  *   residual   u_t + drift + diffusion - phi
  *   scale      |u_t| + |drift| + 1/2 sum_j |a_j^T D^2u a_j| + |phi|: what the residual is
@@ -401,6 +423,26 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
  *                            (with_corr...py:663-700; r, sigma, K = p[0..2])
  *   DBSDE_EXACT_BASKET_MEAN  mean over coordinates of the per-asset BS call
  *                            (with_corr...py:621-660; r, sigma, K = p[0..2])
+ *   DBSDE_EXACT_HESTON       the European call under the two-factor Heston model
+ *                            (DBSDE_PROB_HESTON2 with k = 1): x [R, 2] = (S, v), D == 2
+ *                            (else DBSDE_EINVAL), p = {r, K, kappa, theta, sigma, rho};
+ *                            price = S P1 - K exp(-r tau) P2, delta [R] = dprice/dS = P1,
+ *                            P_j = 1/2 + 1/pi int_0^U Re[exp(-i phi ln K) f_j(phi) / (i phi)] dphi
+ *                            with the branch-stable ("little trap", Albrecher, Mayer,
+ *                            Schoutens, Tistaert 2007) form of the characteristic
+ *                            functions f_j, in fp64 with the kernel's own complex
+ *                            arithmetic.  Quadrature: 64 equal panels of [0, U], an
+ *                            8-point Gauss-Legendre rule on each (one wavefront per
+ *                            point, one panel per lane, the lanes summed by a fixed xor
+ *                            butterfly: bitwise repeatable); U = 8 / sqrt(Vbar) times
+ *                            the first power of sqrt(2) at which |f_j(U)| <= 1e-10 U for
+ *                            both j (at most 2^8), Vbar = theta tau + (v - theta)
+ *                            (1 - exp(-kappa tau)) / kappa the expected integrated
+ *                            variance.  Within 2e-7 (K = 1) of the converged integral on
+ *                            tau in [0.05, 2], v in [0.01, 1], S / K in [0.5, 2] at kappa
+ *                            = 2, theta = 0.2, sigma = 0.3, rho in {0.8, -0.7}
+ *                            (DESIGN 5); outside that domain the rule is unchecked.
+ *                            Needs sigma > 0, K > 0, S > 0, v >= 0.
  * t [R], x [R, D] device fp32; price and delta (nullable) [R * ncol],
  * ncol = D for BS_CALL, 1 otherwise.  At t >= T the payoff and its 0 / 1/2 / 1
  * delta are returned, as the references do.  Computed in fp64.
@@ -409,6 +451,7 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
 #define DBSDE_EXACT_BS_CALL 1
 #define DBSDE_EXACT_BASKET_AVG 2
 #define DBSDE_EXACT_BASKET_MEAN 3
+#define DBSDE_EXACT_HESTON 4
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* hip_stream);
 
@@ -435,8 +478,10 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * mu_eff = mu_a + phi_r phi_c (fp32).  (BSB: mu = 0, sigma = 0.4 X, phi =
  * r (Y - X.Z) gives exp((r + sigma^2) tau) |x|^2 = DBSDE_EXACT_BSB.)  Heston has
  * phi_c = 0 and runs its own clamped drift and 2x2 blocks, one Brownian motion
- * per asset driving both S and v, as the training step does.  phi_zz != 0 (HJB)
- * is DBSDE_EINVAL: use dbsde_hjb_mc.
+ * per asset driving both S and v, as the training step does.  HESTON2 runs its
+ * two-factor step (dbsde_problem above): sample k, asset d draws the Brownian
+ * coordinates d (W^S_d) and D/2 + d (W^v_d); like HESTON it takes neither L nor
+ * delta.  phi_zz != 0 (HJB) is DBSDE_EINVAL: use dbsde_hjb_mc.
  *
  *   L       device [nb, nb] row-major lower Cholesky factor, NULL = independent
  *           increments; DIAG only, nb = D <= 128
