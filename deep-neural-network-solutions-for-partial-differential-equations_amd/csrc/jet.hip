@@ -24,6 +24,7 @@
 #define DBSDE_DEVICE_HELPERS_ONLY
 #include "ctx.hpp"
 #include "jet.hpp"
+#include "sde.hpp"
 
 namespace dbsde {
 
@@ -347,11 +348,9 @@ struct PdeArgs {
   dbsde_pde_terms out;
 };
 
-__device__ __forceinline__ float clamp100(float x) { return fminf(fmaxf(x, -100.f), 100.f); }
-
 // direction 0 = e_t; direction 1 + j = column j of the diffusion matrix:
 // DIAG diag(sig_a X + sig_b) . L; Heston Sigma_j . (1, 1)^T in the (S_j, v_j)
-// plane with the rollout's sqrt(max(v, 1e-8)) and +-100 clamps (paths.hpp),
+// plane with the rollout's own coefficients (heston_coef, sde.hpp),
 // and with a factor L between the assets column j of Sigma(x) . L: for every
 // asset i >= j the (S_i, v_i) entries of Sigma_i . (1, 1)^T times L[i][j];
 // two-factor Heston (nd = 1 + 2k) the 2k columns of its diffusion matrix
@@ -376,19 +375,16 @@ __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
       const int k = a.D >> 1;
       const int i = d < k ? d : d - k;   // the asset of column d
       if (i == (jb < k ? jb : jb - k) && (jb < k || d >= k)) {
-        const float S = x[i], vv = x[k + i];
-        const float sv = sqrtf(fmaxf(vv, 1e-8f));
-        const float sigV = a.pr.h_sigma * sv;
-        v = jb >= k ? clamp100(a.rhob * sigV) : (d < k ? clamp100(sv * S) : clamp100(a.pr.h_rho * sigV));
+        const Heston2Coef h = heston2_coef(a.pr.mu_a, a.pr.h_kappa, a.pr.h_theta, a.pr.h_sigma, a.pr.h_rho, a.rhob,
+                                           x[i], x[k + i]);
+        v = jb >= k ? h.d11 : (d < k ? h.d00 : h.d10);
       }
     } else if (a.heston) {
       const int k = a.nb;
       const int i = d < k ? d : d - k;   // the asset of column d
       if (a.Lt ? i >= jb : i == jb) {
-        const float S = x[i], vv = x[k + i];
-        const float sv = sqrtf(fmaxf(vv, 1e-8f));
-        const float sigS = sv * S, sigV = a.pr.h_sigma * sv;
-        v = d < k ? clamp100(sigS) + clamp100(a.pr.h_rho * sigV) : clamp100(a.pr.h_rho * sigS) + clamp100(sigV);
+        const HestonCoef h = heston_coef(a.pr.mu_a, a.pr.h_kappa, a.pr.h_theta, a.pr.h_sigma, a.pr.h_rho, x[i], x[k + i]);
+        v = d < k ? h.d00 + h.d01 : h.d10 + h.d11;
         if (a.Lt) v *= a.Lt[(size_t)jb * k + i];   // L[i][jb]
       }
     } else {
@@ -420,7 +416,7 @@ __global__ void __launch_bounds__(256) pde_terms_kernel(PdeArgs a) {
     const float xd = x[d], zd = du[d];
     float mu;
     if (a.heston)
-      mu = d < k ? clamp100(a.pr.mu_a * xd) : clamp100(a.pr.h_kappa * (a.pr.h_theta - xd));
+      mu = d < k ? heston_mu_s(a.pr.mu_a, xd) : heston_mu_v(a.pr.h_kappa, a.pr.h_theta, xd);
     else
       mu = a.pr.mu_a * xd;
     drift += mu * zd;

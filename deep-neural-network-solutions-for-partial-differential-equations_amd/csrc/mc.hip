@@ -11,9 +11,9 @@
 // X~ following the problem's Euler scheme with drift coefficient
 // mu_eff = mu_a + phi_r phi_c (fp32, computed once).  Check: BSB has mu = 0,
 // sigma = 0.4 X, phi = r (Y - X.Z): exp((r + sigma^2) tau) |x|^2 = DBSDE_EXACT_BSB.
-// Heston has phi_c = 0 and its own drift and 2x2 blocks, stepped exactly as
-// rollout_heston_kernel steps them; the two-factor Heston (DBSDE_PROB_HESTON2,
-// path kind MC_HESTON2) runs heston2_step (rn.hpp) on two normals per step,
+// Heston has phi_c = 0 and its own drift and 2x2 blocks (heston_step, sde.hpp,
+// as the rollout kernels); the two-factor Heston (DBSDE_PROB_HESTON2,
+// path kind MC_HESTON2) runs heston2_step on two normals per step,
 // those of coordinates d (W^S_d) and nd + d (W^v_d), nd = D / 2 -- the
 // increments rollout_heston2_kernel draws.  phi_zz != 0 (HJB) is not linear:
 // dbsde_hjb_mc.
@@ -24,7 +24,7 @@
 // Point p runs the training grid with T replaced by tau_p = fp32(T) - t_p:
 // t_n = fp32(fp64 cumsum of tau_p / n_steps), dt_n their fp32 differences,
 // sqdt = sqrtf(tau_p / n_steps); the state is fp32 and the step is the
-// reference-order, non-contracted step of paths.hpp.
+// reference-order, non-contracted step of sde.hpp.
 //
 // Layout.  A thread owns (sample k, coordinate d) and carries the state -- and
 // the tangent J when delta is asked for -- of a tile of MC_PT points in
@@ -59,7 +59,7 @@
 
 #include "../../include/dbsde.h"
 #include "philox.hpp"
-#include "rn.hpp"
+#include "sde.hpp"
 
 struct dbsde_ctx;
 int fail(dbsde_ctx* c, int code, const std::string& msg);   // net.hip
@@ -226,23 +226,11 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
           float sa, sb;
           heston2_step(a.mu, a.kappa, a.theta, a.hsig, a.rho, a.rhob, dt, w, rn_mul(sq[i], zv[kk]), X[i], V[i], sa, sb);
         } else if constexpr (KIND == MC_HESTON) {
-          const float S = X[i], v = V[i];
-          const float muS = clamp100(rn_mul(a.mu, S));
-          const float muV = clamp100(rn_mul(a.kappa, rn_sub(a.theta, v)));
-          const float sv = sqrtf(fmaxf(v, 1e-8f));
-          const float sigS = rn_mul(sv, S), sigV = rn_mul(a.hsig, sv);
-          const float d00 = clamp100(sigS), d11 = clamp100(sigV);
-          const float d01 = clamp100(rn_mul(a.rho, sigV)), d10 = clamp100(rn_mul(a.rho, sigS));
-          X[i] = rn_add(rn_add(S, rn_mul(muS, dt)), rn_mul(rn_add(d00, d01), w));
-          V[i] = rn_add(rn_add(v, rn_mul(muV, dt)), rn_mul(rn_add(d10, d11), w));
+          float sa, sb;
+          heston_step(heston_coef(a.mu, a.kappa, a.theta, a.hsig, a.rho, X[i], V[i]), dt, w, X[i], V[i], sa, sb);
         } else {
-          const float x = X[i];
-          const float sg = rn_add(rn_mul(a.sig_a, x), a.sig_b);
-          X[i] = rn_add(rn_add(x, rn_mul(rn_mul(a.mu, x), dt)), rn_mul(sg, w));
-          if constexpr (DELTA) {
-            const float J = V[i];
-            V[i] = rn_add(rn_add(J, rn_mul(rn_mul(a.mu, J), dt)), rn_mul(rn_mul(a.sig_a, J), w));
-          }
+          diag_step(a.mu, a.sig_a, a.sig_b, dt, w, X[i]);
+          if constexpr (DELTA) diag_tangent_step(a.mu, a.sig_a, dt, w, V[i]);
         }
       }
     }

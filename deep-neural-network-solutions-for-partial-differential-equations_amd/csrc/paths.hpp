@@ -17,12 +17,13 @@
 // HIP contracts a*b + c into an FMA by default (-ffp-contract=fast), and its
 // __fmul_rn/__fadd_rn are plain operators whose contract flag comes from the
 // header that defines them, so a pragma at the call site does not stop the
-// fusion.  The path kernels use rn_mul/rn_add/rn_sub of rn.hpp, whose operations
-// carry no contract flag: the reference (torch CPU) rounds each product and
-// sum, and X is bit-exact against it.
+// fusion.  Every kernel here takes its process's step from sde.hpp, where each
+// formula is stated once and each operation is rounded on its own (rn.hpp): the
+// reference (torch CPU) rounds each product and sum, and X is bit-exact against
+// it.
 #pragma once
 #include "philox.hpp"
-#include "rn.hpp"
+#include "sde.hpp"
 
 namespace dbsde {
 
@@ -98,83 +99,96 @@ struct FetchAcc {
 };
 
 // --------------------------------------------------------------------------
-// diagonal problems: thread per (path m, dim d), sequential over n
-//   X1 = (X0 + (mu_a X0) dt) + (sig_a X0 + sig_b) dW   (reference op order,
-//   no contraction; sigma (x) dW is bit-identical to the dense bmm)
+// diagonal problems (diag_step, sde.hpp)
 // --------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) rollout_kernel(RolloutArgs p) {
+// the device fetch_minibatch of a diagonal problem: thread per (path m, dim d),
+// sequential over n
+__global__ void __launch_bounds__(256) fetch_diag_kernel(RolloutArgs p) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= p.M * p.D) return;
   const int m = gid / p.D, d = gid - m * p.D;
   const int N1 = p.N + 1;
-  float x = p.Xi[(p.xi_rows == 1 ? 0 : m) * p.D + d];
   const double dt64 = (double)p.T / (double)p.N;
   const float sqdt = sqrtf(p.T / (float)p.N);
   double tacc = 0.0;
-  float t0 = p.t ? p.t[(size_t)m * N1] : 0.0f;
   float w0 = p.W ? p.W[(size_t)m * N1 * p.nb + d] : 0.0f;
-  size_t r = (size_t)m * N1;
   FetchAcc fa;
-  if (p.out != PATH_ROLLOUT) fa.put(p, m, d, 0, t0, 0.f);
+  fa.put(p, m, d, 0, p.t ? p.t[(size_t)m * N1] : 0.0f, 0.f);
   for (int n0 = 0; n0 < p.N; n0 += 4) {
     float dw[4], t1[4];
     step_block(p, m, d, n0, w0, tacc, dt64, sqdt, dw, t1);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (n0 + k >= p.N) break;
-      if (p.out != PATH_ROLLOUT) {
-        fa.put(p, m, d, n0 + k + 1, t1[k], dw[k]);
-        continue;
-      }
-      float* xr = p.xin + r * p.ldx;
-      xr[1 + d] = x;
-      if (d == 0) {
-        xr[0] = t0;
-        xr[p.D + 1] = 1.0f;
-      }
-      const float dt = rn_sub(t1[k], t0);
-      const float sg = rn_add(rn_mul(p.sig_a, x), p.sig_b);
-      const float s = rn_mul(sg, dw[k]);
-      p.sdw[r * p.ldx + 1 + d] = s;
-      x = rn_add(rn_add(x, rn_mul(rn_mul(p.mu_a, x), dt)), s);
-      t0 = t1[k];
-      ++r;
+      fa.put(p, m, d, n0 + k + 1, t1[k], dw[k]);
     }
-  }
-  if (p.out != PATH_ROLLOUT) return;
-  float* xr = p.xin + r * p.ldx;  // n = N
-  xr[1 + d] = x;
-  p.sdw[r * p.ldx + 1 + d] = 0.0f;
-  if (d == 0) {
-    xr[0] = t0;
-    xr[p.D + 1] = 1.0f;
   }
 }
 
-// The same rollout with whole-row float4 stores: thread per (path m, 16-byte
+// The rollouts write whole rows, 16 bytes per lane: thread per (path m, 16-byte
 // column group c of the xin / sdw rows), columns 4c .. 4c + 3 = t (column 0),
-// X_d (column 1 + d), 1 (column D + 1) and zero padding.  Every row is written
-// whole, 16 bytes per lane: the thread-per-dimension form leaves the padding
-// columns and the misaligned row ends to partial-line writes (the L2 then reads
-// the rest of each line back: 23 MB of reads for a kernel with no inputs,
-// profiles/r3_pmc_fetch).  Per dimension the arithmetic is rollout_kernel's,
-// so X is bit-identical.
+// X_d (column 1 + d), 1 (column D + 1) and zero padding.  (A thread per
+// dimension leaves the padding columns and the misaligned row ends to
+// partial-line writes, and the L2 then reads the rest of each line back: 23 MB
+// of reads for a kernel with no inputs, profiles/r3_pmc_fetch.)  ColGroup is
+// such a thread's state and its stores; what differs between the kernels that
+// use it is where the increments come from.
+struct ColGroup {
+  int c;
+  float x[4];
+  bool live[4];   // the column is a state dimension
+  __device__ __forceinline__ void init(const RolloutArgs& p, int m, int cg) {
+    c = cg;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int d = 4 * c + k - 1;
+      live[k] = d >= 0 && d < p.D;
+      x[k] = live[k] ? p.Xi[(p.xi_rows == 1 ? 0 : m) * p.D + d] : 0.f;
+    }
+  }
+  // the thread's four columns of an xin row at time t0
+  __device__ __forceinline__ floatx4 xcols(const RolloutArgs& p, float t0) const {
+    floatx4 xo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int col = 4 * c + k;
+      xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
+    }
+    return xo;
+  }
+  // row r = m (N + 1) + n, n < N: its xin columns, its sdw columns sigma(X_n) dW_n,
+  // and x <- X_{n+1}
+  __device__ __forceinline__ void put_row(const RolloutArgs& p, size_t r, float t0, float dt, floatx4 dw) {
+    floatx4 xo, so;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int col = 4 * c + k;
+      xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
+      so[k] = live[k] ? diag_step(p.mu_a, p.sig_a, p.sig_b, dt, dw[k], x[k]) : 0.f;
+    }
+    *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xo;
+    *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = so;
+  }
+  // row n = N: X_N and a zero sdw row
+  __device__ __forceinline__ void last_row(const RolloutArgs& p, size_t r, float t0) const {
+    *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xcols(p, t0);
+    *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = floatx4{0.f, 0.f, 0.f, 0.f};
+  }
+};
+
+// One pass: the thread draws (or differences the caller's W) and steps all N
+// steps in sequence.  Parity-mode batches, prefetched rollouts, DBSDE_ROLLOUT2=0.
 __global__ void __launch_bounds__(256) rollout4_kernel(RolloutArgs p) {
   const int C = p.ldx >> 2;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= p.M * C) return;
   const int m = gid / C, c = gid - m * C;
   const int N1 = p.N + 1;
-  float x[4], w0[4];
-  bool live[4];
+  ColGroup g;
+  g.init(p, m, c);
+  float w0[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int d = 4 * c + k - 1;
-    live[k] = d >= 0 && d < p.D;
-    const int dd = live[k] ? d : 0;
-    x[k] = live[k] ? p.Xi[(p.xi_rows == 1 ? 0 : m) * p.D + dd] : 0.f;
-    w0[k] = (live[k] && p.W) ? p.W[(size_t)m * N1 * p.nb + dd] : 0.f;
-  }
+  for (int k = 0; k < 4; ++k) w0[k] = (g.live[k] && p.W) ? p.W[(size_t)m * N1 * p.nb + 4 * c + k - 1] : 0.f;
   const double dt64 = (double)p.T / (double)p.N;
   const float sqdt = sqrtf(p.T / (float)p.N);
   double tacc = 0.0;
@@ -189,7 +203,7 @@ __global__ void __launch_bounds__(256) rollout4_kernel(RolloutArgs p) {
     for (int k = 0; k < 4; ++k) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) dw[k][i] = 0.f;
-      if (live[k]) {
+      if (g.live[k]) {
         tn = tacc;
         step_block(p, m, 4 * c + k - 1, n0, w0[k], tn, dt64, sqdt, dw[k], t1);
       }
@@ -198,148 +212,12 @@ __global__ void __launch_bounds__(256) rollout4_kernel(RolloutArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (n0 + i >= p.N) break;
-      const float dt = rn_sub(t1[i], t0);
-      floatx4 xo, so;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = 4 * c + k;
-        float sv = 0.f;
-        if (live[k]) {
-          const float sg = rn_add(rn_mul(p.sig_a, x[k]), p.sig_b);
-          sv = rn_mul(sg, dw[k][i]);
-        }
-        xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
-        so[k] = sv;
-        if (live[k]) x[k] = rn_add(rn_add(x[k], rn_mul(rn_mul(p.mu_a, x[k]), dt)), sv);
-      }
-      *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xo;
-      *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = so;
+      g.put_row(p, r, t0, rn_sub(t1[i], t0), floatx4{dw[0][i], dw[1][i], dw[2][i], dw[3][i]});
       t0 = t1[i];
       ++r;
     }
   }
-  floatx4 xo, so;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {   // n = N
-    const int col = 4 * c + k;
-    xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
-    so[k] = 0.f;
-  }
-  *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xo;
-  *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = so;
-}
-
-// --------------------------------------------------------------------------
-// Device-mode diagonal rollout with the draws spread over the time steps.
-// rollout4_kernel gives each (path, column group) pair one thread that draws
-// and steps all N steps in sequence: 28 x M threads, a 50-step chain of Philox
-// + Box-Muller + Euler per thread (latency-bound, 33 us at M = 1024 and at
-// M = 128).  Here a 256-thread workgroup owns 64 pairs: the Philox draws of a
-// 16-step window (64 pairs x 4 four-step blocks = 256 tasks, each the 4 live
-// dimensions of one block) go to an LDS buffer, and while waves 1-3 draw the
-// next window into the other buffer, wave 0 -- one lane per pair -- runs the
-// Euler recursion of the current window out of LDS and writes the whole xin /
-// sdw rows.  Per dimension every value is rollout4_kernel's (same Philox key,
-// same sqrt(dt) z, same non-contracted step, the same sequential fp64 time
-// grid), so X is bit-identical.
-// LDS: dw[buf][step in window][pair] as float4 (the pair's 4 columns):
-// lane-linear 16-byte reads, 2 x 16 KB.
-// --------------------------------------------------------------------------
-constexpr int RS_PAIRS = 64;
-constexpr int RS_THREADS = 256;
-constexpr int RS_WIN = 16;                       // steps per window (4 Philox blocks)
-
-__device__ __forceinline__ void rs_draw(const RolloutArgs& p, int g0, int C, int blk0, float sqdt, floatx4* buf,
-                                        int task) {
-  const int pr = task & (RS_PAIRS - 1), bw = task >> 6;   // pair, block within the window
-  const int g = g0 + pr, m = g / C, c = g - m * C;
-  const int b = blk0 + bw;
-  if (m >= p.M || 4 * b >= p.N) return;
-  float dw[4][4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int d = 4 * c + k - 1;
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (d >= 0 && d < p.D) philox_normal4(p.seed, p.offset, (uint32_t)(p.path0 + m), (uint32_t)b, (uint32_t)d, z);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) dw[k][s] = sqdt * z[s];
-  }
-#pragma unroll
-  for (int s = 0; s < 4; ++s) buf[(4 * bw + s) * RS_PAIRS + pr] = floatx4{dw[0][s], dw[1][s], dw[2][s], dw[3][s]};
-}
-
-__global__ void __launch_bounds__(RS_THREADS) rollout_steps_kernel(RolloutArgs p) {
-  __shared__ floatx4 dws[2 * RS_WIN * RS_PAIRS];
-  const int C = p.ldx >> 2;
-  const int g0 = blockIdx.x * RS_PAIRS;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int N1 = p.N + 1, nsb = (p.N + 3) / 4, nw = (nsb + 3) / 4;
-  const float sqdt = sqrtf(p.T / (float)p.N);
-  const double dt64 = (double)p.T / (double)p.N;
-  // window 0: every thread draws one task
-  rs_draw(p, g0, C, 0, sqdt, dws, threadIdx.x);
-  __syncthreads();
-  // the chain lane's state (wave 0)
-  const int g = g0 + lane, m = g / C, c = g - m * C;
-  const bool ok = wave == 0 && m < p.M;
-  float x[4];
-  bool live[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int d = 4 * c + k - 1;
-    live[k] = d >= 0 && d < p.D;
-    x[k] = (ok && live[k]) ? p.Xi[(p.xi_rows == 1 ? 0 : m) * p.D + d] : 0.f;
-  }
-  double tacc = 0.0;
-  float t0 = (ok && p.t) ? p.t[(size_t)m * N1] : 0.0f;
-  for (int w = 0; w < nw; ++w) {
-    if (wave != 0) {
-      // the next window's 256 tasks over the 192 drawing threads
-      if (w + 1 < nw)
-        for (int task = threadIdx.x - 64; task < RS_WIN / 4 * RS_PAIRS; task += RS_THREADS - 64)
-          rs_draw(p, g0, C, 4 * (w + 1), sqdt, dws + ((w + 1) & 1) * RS_WIN * RS_PAIRS, task);
-    } else if (ok) {
-      const floatx4* buf = dws + (w & 1) * RS_WIN * RS_PAIRS;
-      for (int i = 0; i < RS_WIN; ++i) {
-        const int n = RS_WIN * w + i;
-        if (n >= p.N) break;
-        tacc += dt64;
-        const float t1 = p.t ? p.t[(size_t)m * N1 + n + 1] : (float)tacc;
-        const floatx4 dw = buf[i * RS_PAIRS + lane];
-        const float dt = rn_sub(t1, t0);
-        floatx4 xo, so;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int col = 4 * c + k;
-          float sv = 0.f;
-          if (live[k]) {
-            const float sg = rn_add(rn_mul(p.sig_a, x[k]), p.sig_b);
-            sv = rn_mul(sg, dw[k]);
-          }
-          xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
-          so[k] = sv;
-          if (live[k]) x[k] = rn_add(rn_add(x[k], rn_mul(rn_mul(p.mu_a, x[k]), dt)), sv);
-        }
-        const size_t r = (size_t)m * N1 + n;
-        *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xo;
-        *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = so;
-        t0 = t1;
-      }
-    }
-    __syncthreads();
-  }
-  if (!ok) return;
-  floatx4 xo, so;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {   // n = N
-    const int col = 4 * c + k;
-    xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
-    so[k] = 0.f;
-  }
-  const size_t r = (size_t)m * N1 + p.N;
-  *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xo;
-  *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = so;
+  g.last_row(p, r, t0);
 }
 
 // --------------------------------------------------------------------------
@@ -394,14 +272,8 @@ __global__ void __launch_bounds__(RC_THREADS) rollout_chain_kernel(RolloutArgs p
   if (gid >= p.M * C) return;
   const int m = gid / C, c = gid - m * C;
   const int N1 = p.N + 1;
-  float x[4];
-  bool live[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int d = 4 * c + k - 1;
-    live[k] = d >= 0 && d < p.D;
-    x[k] = live[k] ? p.Xi[(p.xi_rows == 1 ? 0 : m) * p.D + d] : 0.f;
-  }
+  ColGroup g;
+  g.init(p, m, c);
   const double dt64 = (double)p.T / (double)p.N;
   double tacc = 0.0;
   float t0 = 0.0f;
@@ -419,34 +291,11 @@ __global__ void __launch_bounds__(RC_THREADS) rollout_chain_kernel(RolloutArgs p
       tacc += dt64;
       float t1 = (float)tacc;
       if constexpr (HOST_T) t1 = p.t[(size_t)m * N1 + n + 1];
-      const float dt = rn_sub(t1, t0);
-      floatx4 xo, so;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = 4 * c + k;
-        float sv = 0.f;
-        if (live[k]) {
-          const float sg = rn_add(rn_mul(p.sig_a, x[k]), p.sig_b);
-          sv = rn_mul(sg, dw[i][k]);
-        }
-        xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
-        so[k] = sv;
-        if (live[k]) x[k] = rn_add(rn_add(x[k], rn_mul(rn_mul(p.mu_a, x[k]), dt)), sv);
-      }
-      *(floatx4*)(p.xin + (r0 + n) * p.ldx + 4 * c) = xo;
-      *(floatx4*)(p.sdw + (r0 + n) * p.ldx + 4 * c) = so;
+      g.put_row(p, r0 + n, t0, rn_sub(t1, t0), dw[i]);
       t0 = t1;
     }
   }
-  floatx4 xo, so;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {   // n = N
-    const int col = 4 * c + k;
-    xo[k] = col == 0 ? t0 : (col == p.D + 1 ? 1.f : x[k]);
-    so[k] = 0.f;
-  }
-  *(floatx4*)(p.xin + (r0 + p.N) * p.ldx + 4 * c) = xo;
-  *(floatx4*)(p.sdw + (r0 + p.N) * p.ldx + 4 * c) = so;
+  g.last_row(p, r0 + p.N, t0);
 }
 
 // --------------------------------------------------------------------------
@@ -627,10 +476,7 @@ __device__ __forceinline__ void corr_wave(const RolloutArgs& p, float* xs, float
             }
             float* sr = stg + (n & 1) * G::STAGE + cl * G::SROW;
             sr[1 + d] = x[oc][r];
-            const float sg = rn_add(rn_mul(p.sig_a, x[oc][r]), p.sig_b);
-            const float sv = rn_mul(sg, dw);
-            sr[CP_PATHS * G::SROW + 1 + d] = sv;
-            x[oc][r] = rn_add(rn_add(x[oc][r], rn_mul(rn_mul(p.mu_a, x[oc][r]), dt)), sv);
+            sr[CP_PATHS * G::SROW + 1 + d] = diag_step(p.mu_a, p.sig_a, p.sig_b, dt, dw, x[oc][r]);
           }
         if (writes_t && p.out == PATH_ROLLOUT) {
           float* sr = stg + (n & 1) * G::STAGE + cl * G::SROW;
@@ -835,23 +681,60 @@ __global__ void __launch_bounds__(256) corrw_fetch_kernel(RolloutArgs p) {
 }
 
 // --------------------------------------------------------------------------
-// k-asset Heston (heston_dnnpde.py:587-605, 629-642), state [S_1..S_k,
-// v_1..v_k], one scalar Brownian motion per asset that drives both S and v
-// (the reference's FBSNN dimension is 1 and einsum broadcasts dW over the two
-// state components).  Thread per (path m, asset i):
-//   mu    = clamp([0.05 S, kappa (theta - v)], +-100)
-//   sv    = sqrt(max(v, 1e-8));  Sig = clamp([[sv S, rho sig sv], [rho sv S, sig sv]], +-100)
-//   X1    = (X0 + mu dt) + (Sig_i0 + Sig_i1) dW     (einsum sums over j first)
-//   sdw_i = Sig_i0 dW + Sig_i1 dW                   (the Y-tilde term, :641-642)
+// The Heston kernels: state [S_1..S_k, v_1..v_k], thread per (path m, asset
+// i), sequential over n.  AssetRows is such a thread's state and its share of
+// the rows: columns 1 + i (S_i) and 1 + k + i (v_i) of xin and sdw, and for
+// asset 0 also t (column 0) and the constant 1 (column D + 1).  A wave's 64
+// threads store two runs of up to 256 contiguous bytes per row and array.
 // --------------------------------------------------------------------------
+struct AssetRows {
+  int i, k;
+  float S, v;
+  __device__ __forceinline__ void init(const RolloutArgs& p, int m, int asset, int assets) {
+    i = asset;
+    k = assets;
+    const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
+    S = xi[i];
+    v = xi[k + i];
+  }
+  __device__ __forceinline__ void put_x(const RolloutArgs& p, size_t r, float t0) const {
+    float* xr = p.xin + r * p.ldx;
+    xr[1 + i] = S;
+    xr[1 + k + i] = v;
+    if (i == 0) {
+      xr[0] = t0;
+      xr[p.D + 1] = 1.0f;
+    }
+  }
+  __device__ __forceinline__ void put_s(const RolloutArgs& p, size_t r, float a, float b) const {
+    p.sdw[r * p.ldx + 1 + i] = a;
+    p.sdw[r * p.ldx + 1 + k + i] = b;
+  }
+  // row n = N: X_N and a zero sdw row
+  __device__ __forceinline__ void last_row(const RolloutArgs& p, size_t r, float t0) const {
+    put_x(p, r, t0);
+    put_s(p, r, 0.0f, 0.0f);
+  }
+  // row n < N of the one-factor model (heston_step, sde.hpp), increment w
+  __device__ __forceinline__ void heston_row(const RolloutArgs& p, size_t r, float t0, float t1, float w) {
+    put_x(p, r, t0);
+    float a, b;
+    heston_step(heston_coef(p.mu_a, p.kappa, p.theta, p.hsig, p.rho, S, v), rn_sub(t1, t0), w, S, v, a, b);
+    put_s(p, r, a, b);
+  }
+};
+
+// k-asset Heston (heston_dnnpde.py), one scalar Brownian motion per asset:
+// parity-mode batches (the caller's W), contexts without a factor, and their
+// fetch
 __global__ void __launch_bounds__(256) rollout_heston_kernel(RolloutArgs p) {
   const int k = p.nb;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= p.M * k) return;
   const int m = gid / k, i = gid - m * k;
   const int N1 = p.N + 1;
-  const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
-  float S = xi[i], v = xi[k + i];
+  AssetRows g;
+  g.init(p, m, i, k);
   const double dt64 = (double)p.T / (double)p.N;
   const float sqdt = sqrtf(p.T / (float)p.N);
   double tacc = 0.0;
@@ -870,39 +753,12 @@ __global__ void __launch_bounds__(256) rollout_heston_kernel(RolloutArgs p) {
         fa.put(p, m, i, n0 + kk + 1, t1[kk], dw[kk]);
         continue;
       }
-      float* xr = p.xin + r * p.ldx;
-      xr[1 + i] = S;
-      xr[1 + k + i] = v;
-      if (i == 0) {
-        xr[0] = t0;
-        xr[p.D + 1] = 1.0f;
-      }
-      const float dt = rn_sub(t1[kk], t0);
-      const float muS = clamp100(rn_mul(p.mu_a, S));
-      const float muV = clamp100(rn_mul(p.kappa, rn_sub(p.theta, v)));
-      const float sv = sqrtf(fmaxf(v, 1e-8f));   // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt)
-      const float sigS = rn_mul(sv, S), sigV = rn_mul(p.hsig, sv);
-      const float d00 = clamp100(sigS), d11 = clamp100(sigV);
-      const float d01 = clamp100(rn_mul(p.rho, sigV)), d10 = clamp100(rn_mul(p.rho, sigS));
-      const float w = dw[kk];
-      p.sdw[r * p.ldx + 1 + i] = rn_add(rn_mul(d00, w), rn_mul(d01, w));
-      p.sdw[r * p.ldx + 1 + k + i] = rn_add(rn_mul(d10, w), rn_mul(d11, w));
-      S = rn_add(rn_add(S, rn_mul(muS, dt)), rn_mul(rn_add(d00, d01), w));
-      v = rn_add(rn_add(v, rn_mul(muV, dt)), rn_mul(rn_add(d10, d11), w));
+      g.heston_row(p, r, t0, t1[kk], dw[kk]);
       t0 = t1[kk];
       ++r;
     }
   }
-  if (p.out != PATH_ROLLOUT) return;
-  float* xr = p.xin + r * p.ldx;
-  xr[1 + i] = S;
-  xr[1 + k + i] = v;
-  p.sdw[r * p.ldx + 1 + i] = 0.0f;
-  p.sdw[r * p.ldx + 1 + k + i] = 0.0f;
-  if (i == 0) {
-    xr[0] = t0;
-    xr[p.D + 1] = 1.0f;
-  }
+  if (p.out == PATH_ROLLOUT) g.last_row(p, r, t0);
 }
 
 // --------------------------------------------------------------------------
@@ -915,9 +771,9 @@ __global__ void __launch_bounds__(256) rollout_heston_kernel(RolloutArgs p) {
 //     sdw[row, 1 + i] is the S_i column of a Heston row (D = 2 k), which parks
 //     asset i's increment of step n in row n.
 //   pass 2 (rollout_heston_chain_kernel): thread per (path, asset) runs
-//     rollout_heston_kernel's step (the same rn_* operations, correctly rounded
-//     sqrt, +-100 clamps and fp64 time grid, so with L = I the paths are
-//     bit-identical to the uncorrelated kernel's), reading its increments
+//     rollout_heston_kernel's rows (AssetRows::heston_row on the same fp64 time
+//     grid, so with L = I the paths are bit-identical to the uncorrelated
+//     kernel's), reading its increments
 //     RC_AHEAD rows ahead of the chain, and overwrites sdw[row, 1 + i] and
 //     sdw[row, 1 + k + i] with the Y-tilde term.  A thread reads and writes
 //     only its own asset's columns (asset 0's thread also t and the constant
@@ -939,8 +795,8 @@ __global__ void __launch_bounds__(256) rollout_heston_chain_kernel(RolloutArgs p
   if (gid >= p.M * k) return;
   const int m = gid / k, i = gid - m * k;
   const int N1 = p.N + 1;
-  const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
-  float S = xi[i], v = xi[k + i];
+  AssetRows g;
+  g.init(p, m, i, k);
   const double dt64 = (double)p.T / (double)p.N;
   double tacc = 0.0;
   float t0 = 0.0f;
@@ -957,39 +813,11 @@ __global__ void __launch_bounds__(256) rollout_heston_chain_kernel(RolloutArgs p
       tacc += dt64;
       float t1 = (float)tacc;
       if constexpr (HOST_T) t1 = p.t[(size_t)m * N1 + n + 1];
-      float* xr = p.xin + (r0 + n) * p.ldx;
-      float* sr = p.sdw + (r0 + n) * p.ldx;
-      xr[1 + i] = S;
-      xr[1 + k + i] = v;
-      if (i == 0) {
-        xr[0] = t0;
-        xr[p.D + 1] = 1.0f;
-      }
-      const float dt = rn_sub(t1, t0);
-      const float muS = clamp100(rn_mul(p.mu_a, S));
-      const float muV = clamp100(rn_mul(p.kappa, rn_sub(p.theta, v)));
-      const float sv = sqrtf(fmaxf(v, 1e-8f));   // correctly rounded, as in rollout_heston_kernel
-      const float sigS = rn_mul(sv, S), sigV = rn_mul(p.hsig, sv);
-      const float d00 = clamp100(sigS), d11 = clamp100(sigV);
-      const float d01 = clamp100(rn_mul(p.rho, sigV)), d10 = clamp100(rn_mul(p.rho, sigS));
-      const float w = dw[a];
-      sr[1 + i] = rn_add(rn_mul(d00, w), rn_mul(d01, w));
-      sr[1 + k + i] = rn_add(rn_mul(d10, w), rn_mul(d11, w));
-      S = rn_add(rn_add(S, rn_mul(muS, dt)), rn_mul(rn_add(d00, d01), w));
-      v = rn_add(rn_add(v, rn_mul(muV, dt)), rn_mul(rn_add(d10, d11), w));
+      g.heston_row(p, r0 + n, t0, t1, dw[a]);
       t0 = t1;
     }
   }
-  float* xr = p.xin + (r0 + p.N) * p.ldx;   // n = N
-  float* sr = p.sdw + (r0 + p.N) * p.ldx;
-  xr[1 + i] = S;
-  xr[1 + k + i] = v;
-  sr[1 + i] = 0.0f;
-  sr[1 + k + i] = 0.0f;
-  if (i == 0) {
-    xr[0] = t0;
-    xr[p.D + 1] = 1.0f;
-  }
+  g.last_row(p, r0 + p.N, t0);
 }
 
 // --------------------------------------------------------------------------
@@ -999,19 +827,11 @@ __global__ void __launch_bounds__(256) rollout_heston_chain_kernel(RolloutArgs p
 // per (path m, asset i), sequential over n; per 4-step Philox block it draws
 // coordinates i and k + i with the diagonal rollout's key (seed, offset, global
 // path, step block, coordinate), so the increments are those of a diagonal
-// problem with D = 2k.  The step, every operation rounded on its own (rn_*,
-// correctly rounded sqrt, c = clamp100), w1 / w2 the increments of W^S_i / W^v_i:
-//   sv  = sqrt(max(v, 1e-8))
-//   muS = c(mu_a S)          muV = c(kappa (theta - v))
-//   d00 = c(sv S)            d10 = c(rho (sig sv))         d11 = c(rhob (sig sv))
-//   a   = d00 w1             b   = d10 w1 + d11 w2         (the sdw columns S_i, v_i)
-//   S1  = (S + muS dt) + a   v1  = (v + muV dt) + b
-// rhob = fp32(sqrt(1 - (double)rho^2)) comes from the host.  One kernel serves
-// the rollout (device grid or the caller's t / W [M, N+1, 2k]) and the two
-// fetch outputs.  A wave's 64 threads store two runs of up to 256 contiguous
-// bytes per row and array, as rollout_heston_kernel does.
+// problem with D = 2k.  The step is heston2_step (sde.hpp), w1 / w2 the
+// increments of W^S_i / W^v_i; rhob = fp32(sqrt(1 - (double)rho^2)) comes from
+// the host.  One kernel serves the rollout (device grid or the caller's t /
+// W [M, N+1, 2k]) and the two fetch outputs.
 // --------------------------------------------------------------------------
-// The step itself is heston2_step (rn.hpp), shared with the Monte-Carlo comparator.
 constexpr int H2_THREADS = 256;
 __global__ void __launch_bounds__(H2_THREADS) rollout_heston2_kernel(RolloutArgs p) {
   const int k = p.D >> 1;   // nb = D = 2k
@@ -1019,8 +839,8 @@ __global__ void __launch_bounds__(H2_THREADS) rollout_heston2_kernel(RolloutArgs
   if (gid >= p.M * k) return;
   const int m = gid / k, i = gid - m * k;
   const int N1 = p.N + 1;
-  const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
-  float S = xi[i], v = xi[k + i];
+  AssetRows g;
+  g.init(p, m, i, k);
   const double dt64 = (double)p.T / (double)p.N;
   const float sqdt = sqrtf(p.T / (float)p.N);
   double tacc = 0.0;
@@ -1047,31 +867,15 @@ __global__ void __launch_bounds__(H2_THREADS) rollout_heston2_kernel(RolloutArgs
         fv.put(p, m, k + i, n0 + kk + 1, t1[kk], dwv[kk]);
         continue;
       }
-      float* xr = p.xin + r * p.ldx;
-      xr[1 + i] = S;
-      xr[1 + k + i] = v;
-      if (i == 0) {
-        xr[0] = t0;
-        xr[p.D + 1] = 1.0f;
-      }
+      g.put_x(p, r, t0);
       float a, b;
-      heston2_step(p.mu_a, p.kappa, p.theta, p.hsig, p.rho, p.rhob, rn_sub(t1[kk], t0), dws[kk], dwv[kk], S, v, a, b);
-      p.sdw[r * p.ldx + 1 + i] = a;
-      p.sdw[r * p.ldx + 1 + k + i] = b;
+      heston2_step(p.mu_a, p.kappa, p.theta, p.hsig, p.rho, p.rhob, rn_sub(t1[kk], t0), dws[kk], dwv[kk], g.S, g.v, a, b);
+      g.put_s(p, r, a, b);
       t0 = t1[kk];
       ++r;
     }
   }
-  if (p.out != PATH_ROLLOUT) return;
-  float* xr = p.xin + r * p.ldx;   // n = N
-  xr[1 + i] = S;
-  xr[1 + k + i] = v;
-  p.sdw[r * p.ldx + 1 + i] = 0.0f;
-  p.sdw[r * p.ldx + 1 + k + i] = 0.0f;
-  if (i == 0) {
-    xr[0] = t0;
-    xr[p.D + 1] = 1.0f;
-  }
+  if (p.out == PATH_ROLLOUT) g.last_row(p, r, t0);
 }
 
 // Q3 (D == 1): S_n = sum over paths of sdw[m, n]   (1d_BSPDE_case.py:271-273)

@@ -16,16 +16,8 @@
 // device-mode diagonal rollout: in-step by default the two-pass form (parallel
 // draws into the sdw rows, then the Euler chains: rollout_draw_kernel +
 // rollout_chain_kernel, ctx rollout2; DBSDE_ROLLOUT2=0 turns it off: M = 128
-// 0.146 vs 0.156 ms/step, profiles/r6_ab_rollout.txt 4); prefetched, and else, the
-// draws spread over the time steps (rollout_steps_kernel, DBSDE_RS = 1) or one
-// thread per (path, column group) for all steps (rollout4_kernel, 0).  The prefetched rollout is off the step's
-// critical path either way (0.4472 vs 0.4445 ms/step at M = 1024, 0.140 vs
-// 0.140 at M = 128), but beside the phase section of a profiled step the
-// step-parallel kernel's 4-wave, 32 KB-LDS workgroups slow the section by
-// ~13 us: off (profiles/r6_ab_phase.txt 4).
-#ifndef DBSDE_RS
-#define DBSDE_RS 0
-#endif
+// 0.146 vs 0.156 ms/step, profiles/r6_ab_rollout.txt 4); prefetched, and else,
+// one thread per (path, column group) for all steps (rollout4_kernel).
 #define DBSDE_DEVICE_HELPERS_ONLY
 #include "ctx.hpp"
 #include "paths.hpp"
@@ -125,6 +117,8 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
   const char* name = ra.out == PATH_ROLLOUT ? "rollout" : "brownian";
   const double steps = (double)ra.M * ra.N;
   const double bytes = ra.out == PATH_ROLLOUT ? 4.0 * steps * (2.0 * ra.D + (ra.W ? ra.nb : 0)) : 4.0 * steps * ra.nb;
+  // the rollouts store whole float4 columns of the rows (ldx = Dp = pad16(D + 2))
+  if (ra.ldx % 4 != 0) return fail(c, DBSDE_EINVAL, "internal: path row stride is not a multiple of 4 floats");
   if (c->heston2) {
     // two-factor Heston (never with a factor: dbsde_set_corr refuses it): one
     // kernel for device- and parity-mode batches, in-step and prefetched, and
@@ -136,7 +130,7 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
     // wide correlated device mode, and correlated Heston at every k (paths.hpp):
     // the triangular GEMM dW = L (sqrt(dt) z) over (path group, step block),
     // then the Euler chains or the fetch sums
-    if (ra.ldx % 4 != 0 || ra.nb > CW_OB * 8 * 16 || ra.nb * (c->heston ? 2 : 1) != ra.D)
+    if (ra.nb > CW_OB * 8 * 16 || ra.nb * (c->heston ? 2 : 1) != ra.D)
       return fail(c, DBSDE_EINVAL, "internal: wide correlated rollout geometry");
     const dim3 g((ra.M + CW_PATHS - 1) / CW_PATHS, (ra.N + 3) / 4);
     const double fl = 2.0 * steps * ra.nb * ra.nb / 2;
@@ -165,27 +159,23 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
     const int nthr = ra.M * ra.nb;
     RUN(c, s, name, 0.0, bytes, rollout_heston_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
   } else if (c->Lt && !ra.W) {
-    if (ra.ldx > cp_srow((ra.nb + 15) / 16) || ra.ldx % 4 != 0)
+    if (ra.ldx > cp_srow((ra.nb + 15) / 16))
       return fail(c, DBSDE_EINVAL, "internal: correlated rollout row staging");
     RUN(c, s, name, 2.0 * steps * ra.nb * ra.nb / 2, bytes,
         launch_corr(ra, s));
-  } else if (c->rollout2 && !side && ra.out == PATH_ROLLOUT && !ra.W && !ra.t && ra.ldx % 4 == 0) {
+  } else if (c->rollout2 && !side && ra.out == PATH_ROLLOUT && !ra.W && !ra.t) {
     // device-mode increments: parallel draws, then the Euler chains (paths.hpp)
     const long long draws = (long long)ra.M * ((ra.N + 3) / 4) * (ra.ldx / 4);
     const int chains = ra.M * (ra.ldx / 4);
     RUN(c, s, name, 0.0, bytes,
         rollout_draw_kernel<<<(unsigned)((draws + 255) / 256), 256, 0, s>>>(ra);
         rollout_chain_kernel<false><<<(unsigned)((chains + RC_THREADS - 1) / RC_THREADS), RC_THREADS, 0, s>>>(ra));
-  } else if (DBSDE_RS && ra.out == PATH_ROLLOUT && !ra.W && ra.ldx % 4 == 0) {
-    // device-mode increments: draws spread over the time steps (paths.hpp)
-    const long long pairs = (long long)ra.M * (ra.ldx / 4);
-    RUN(c, s, name, 0.0, bytes, rollout_steps_kernel<<<(unsigned)((pairs + RS_PAIRS - 1) / RS_PAIRS), RS_THREADS, 0, s>>>(ra));
-  } else if (ra.out == PATH_ROLLOUT && ra.ldx % 4 == 0) {
-    const int nthr = ra.M * (ra.ldx / 4);   // whole-row float4 stores
+  } else if (ra.out == PATH_ROLLOUT) {
+    const int nthr = ra.M * (ra.ldx / 4);
     RUN(c, s, name, 0.0, bytes, rollout4_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
   } else {
     const int nthr = ra.M * ra.D;
-    RUN(c, s, name, 0.0, bytes, rollout_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
+    RUN(c, s, name, 0.0, bytes, fetch_diag_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
   }
   return DBSDE_OK;
 }

@@ -1,0 +1,95 @@
+// sde.hpp -- the one definition of each process's Euler-Maruyama step.
+//
+// Every path kernel (paths.hpp), the Monte-Carlo comparator (mc.hip) and the
+// Heston coefficients of the PDE residual (jet.hip) take their step from here,
+// so X is the numpy oracle's bit for bit (oracle/philox.py,
+// tests/heston2_reference.py) and every rollout form equals every other.  Each
+// product and sum is rounded on its own (rn.hpp), the square root is correctly
+// rounded (hipcc's default for fp32), c = clamp100.  The header is plain C++
+// without hipcc, and tests/test_sde_step_cpu.py checks these functions against
+// the oracles on a CPU.
+#pragma once
+#include "rn.hpp"
+
+namespace dbsde {
+
+// Diagonal problems (DeepBSDE.py:218-222 with mu = mu_a X, sigma = diag(sig_a X
+// + sig_b); sigma (x) dW is bit-identical to the dense bmm):
+//   s = (sig_a x + sig_b) dw,   x <- (x + (mu_a x) dt) + s
+// returns s, the sdw entry of the row x came from
+DBSDE_HD float diag_step(float mu_a, float sig_a, float sig_b, float dt, float dw, float& x) {
+  const float s = rn_mul(rn_add(rn_mul(sig_a, x), sig_b), dw);
+  x = rn_add(rn_add(x, rn_mul(rn_mul(mu_a, x), dt)), s);
+  return s;
+}
+
+// the tangent J = dx / dx_0 of that step (sig_b drops out)
+DBSDE_HD void diag_tangent_step(float mu_a, float sig_a, float dt, float dw, float& J) {
+  J = rn_add(rn_add(J, rn_mul(rn_mul(mu_a, J), dt)), rn_mul(rn_mul(sig_a, J), dw));
+}
+
+// What the two Heston models share at a state (S, v) of one asset: the drifts
+//   muS = c(mu_a S),   muV = c(kappa (theta - v))
+// and, with sv = sqrt(max(v, 1e-8)), sigS = sv S, sigV = sig sv (unclamped) and
+// d00 = c(sigS).
+DBSDE_HD float heston_mu_s(float mu_a, float S) { return clamp100(rn_mul(mu_a, S)); }
+DBSDE_HD float heston_mu_v(float kappa, float theta, float v) { return clamp100(rn_mul(kappa, rn_sub(theta, v))); }
+struct HestonBase {
+  float muS, muV, sigS, sigV, d00;
+};
+DBSDE_HD HestonBase heston_base(float mu_a, float kappa, float theta, float hsig, float S, float v) {
+  HestonBase b;
+  b.muS = heston_mu_s(mu_a, S);
+  b.muV = heston_mu_v(kappa, theta, v);
+  const float sv = sqrtf(fmaxf(v, 1e-8f));
+  b.sigS = rn_mul(sv, S);
+  b.sigV = rn_mul(hsig, sv);
+  b.d00 = clamp100(b.sigS);
+  return b;
+}
+
+// k-asset Heston (heston_dnnpde.py:587-605, 629-642): one scalar Brownian
+// motion per asset drives both S and v (the reference's FBSNN dimension is 1
+// and einsum broadcasts dW over the two state components).
+//   Sig = c([[sv S, rho sig sv], [rho sv S, sig sv]]) = [[d00, d01], [d10, d11]]
+//   a = d00 w + d01 w,   b = d10 w + d11 w       (the Y-tilde term, :641-642)
+//   S <- (S + muS dt) + (d00 + d01) w,   v <- (v + muV dt) + (d10 + d11) w
+//                                                (einsum sums over j first)
+struct HestonCoef {
+  float muS, muV, d00, d01, d10, d11;
+};
+DBSDE_HD HestonCoef heston_coef(float mu_a, float kappa, float theta, float hsig, float rho, float S, float v) {
+  const HestonBase b = heston_base(mu_a, kappa, theta, hsig, S, v);
+  return HestonCoef{b.muS, b.muV, b.d00, clamp100(rn_mul(rho, b.sigV)), clamp100(rn_mul(rho, b.sigS)), clamp100(b.sigV)};
+}
+// a and b are the sdw entries of the S and v columns
+DBSDE_HD void heston_step(const HestonCoef& c, float dt, float w, float& S, float& v, float& a, float& b) {
+  a = rn_add(rn_mul(c.d00, w), rn_mul(c.d01, w));
+  b = rn_add(rn_mul(c.d10, w), rn_mul(c.d11, w));
+  S = rn_add(rn_add(S, rn_mul(c.muS, dt)), rn_mul(rn_add(c.d00, c.d01), w));
+  v = rn_add(rn_add(v, rn_mul(c.muV, dt)), rn_mul(rn_add(c.d10, c.d11), w));
+}
+
+// Two-factor Heston (DBSDE_PROB_HESTON2, include/dbsde.h): the textbook model,
+// w1 / w2 the increments of W^S and W^v, rhob = fp32(sqrt(1 - (double)rho^2)):
+//   d10 = c(rho sigV),   d11 = c(rhob sigV)
+//   a = d00 w1,   b = d10 w1 + d11 w2            (the sdw columns S, v)
+//   S <- (S + muS dt) + a,   v <- (v + muV dt) + b
+struct Heston2Coef {
+  float muS, muV, d00, d10, d11;
+};
+DBSDE_HD Heston2Coef heston2_coef(float mu_a, float kappa, float theta, float hsig, float rho, float rhob, float S,
+                                  float v) {
+  const HestonBase b = heston_base(mu_a, kappa, theta, hsig, S, v);
+  return Heston2Coef{b.muS, b.muV, b.d00, clamp100(rn_mul(rho, b.sigV)), clamp100(rn_mul(rhob, b.sigV))};
+}
+DBSDE_HD void heston2_step(float mu_a, float kappa, float theta, float hsig, float rho, float rhob, float dt, float w1,
+                           float w2, float& S, float& v, float& a, float& b) {
+  const Heston2Coef c = heston2_coef(mu_a, kappa, theta, hsig, rho, rhob, S, v);
+  a = rn_mul(c.d00, w1);
+  b = rn_add(rn_mul(c.d10, w1), rn_mul(c.d11, w2));
+  S = rn_add(rn_add(S, rn_mul(c.muS, dt)), a);
+  v = rn_add(rn_add(v, rn_mul(c.muV, dt)), b);
+}
+
+}  // namespace dbsde

@@ -1,9 +1,10 @@
 """ORACLE -- test infrastructure only, never the product path.
 
 NumPy restatement of the device-mode Brownian increments and path step of the
-HIP library (throughput mode, dbsde_batch.W == NULL; csrc/philox.hpp,
-csrc/paths.hpp rollout_kernel / rollout_corr_kernel / rollout_heston_kernel,
-dbsde_brownian):
+HIP library (throughput mode, dbsde_batch.W == NULL; csrc/philox.hpp, the steps
+of csrc/sde.hpp as every kernel of csrc/paths.hpp runs them -- rollout4_kernel,
+rollout_chain_kernel, rollout_corr_kernel, rollout_heston_kernel,
+rollout_heston_chain_kernel -- and dbsde_brownian):
 
   * Philox4x32-10 (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: as
     easy as 1, 2, 3", SC'11; the Random123 round constants), counter
@@ -94,24 +95,34 @@ def brownian_W(dw):
     return W.astype(np.float32)
 
 
-def rollout(Xi, dw, T, mu_a=0.0, sig_a=0.0, sig_b=0.0):
+def _dts(N, T, tgrid):
+    """The fp32 time steps [N] of the reference grid, or [N] columns [M, 1] of a
+    caller's grid tgrid [M, N+1]."""
+    if tgrid is None:
+        tg = time_grid(N, T)
+        return [np.float32(tg[n + 1] - tg[n]) for n in range(N)]
+    tg = np.asarray(tgrid, np.float32).reshape(-1, N + 1)
+    return [(tg[:, n + 1] - tg[:, n])[:, None] for n in range(N)]
+
+
+def rollout(Xi, dw, T, mu_a=0.0, sig_a=0.0, sig_b=0.0, tgrid=None):
     """X [M, N+1, D] float32: x1 = (x + (mu_a x) dt) + (sig_a x + sig_b) dw on the
-    reference grid."""
+    reference grid, or on a caller's grid tgrid [M, N+1]."""
     M, N, D = dw.shape
     f32 = np.float32
     x = np.broadcast_to(np.asarray(Xi, f32).reshape(-1, D), (M, D)).astype(f32)
     X = np.empty((M, N + 1, D), f32)
-    tg = time_grid(N, T)
+    dts = _dts(N, T, tgrid)
     for n in range(N):
         X[:, n] = x
-        dt = f32(tg[n + 1] - tg[n])
+        dt = dts[n]
         s = (f32(sig_a) * x + f32(sig_b)) * dw[:, n]
         x = (x + (f32(mu_a) * x) * dt) + s
     X[:, N] = x
     return X
 
 
-def heston_rollout(Xi, dw, T, mu_a=0.05, kappa=2.0, theta=0.2, sigma=0.3, rho=0.8):
+def heston_rollout(Xi, dw, T, mu_a=0.05, kappa=2.0, theta=0.2, sigma=0.3, rho=0.8, tgrid=None):
     """k-asset Heston state [S_1..S_k, v_1..v_k] (heston_dnnpde.py:587-605,
     629-642): mu and the diffusion blocks clamped to [-100, 100], one dW per
     asset; the X update uses (Sig_i0 + Sig_i1) dW (torch.einsum sums the
@@ -123,11 +134,11 @@ def heston_rollout(Xi, dw, T, mu_a=0.05, kappa=2.0, theta=0.2, sigma=0.3, rho=0.
     S, v = x[:, :k].copy(), x[:, k:].copy()
     X = np.empty((M, N + 1, 2 * k), f32)
     sdw = np.empty((M, N, 2 * k), f32)
-    tg = time_grid(N, T)
+    dts = _dts(N, T, tgrid)
     c = lambda a: np.clip(a, f32(-100), f32(100))
     for n in range(N):
         X[:, n, :k], X[:, n, k:] = S, v
-        dt = f32(tg[n + 1] - tg[n])
+        dt = dts[n]
         muS, muV = c(f32(mu_a) * S), c(f32(kappa) * (f32(theta) - v))
         sv = np.sqrt(np.maximum(v, f32(1e-8)))
         sS, sV = sv * S, f32(sigma) * sv

@@ -135,6 +135,24 @@ def test_paths_are_the_oracle_rollout_of_the_device_increments(pkg, dev, k):
         np.testing.assert_array_equal(X, Xr)
 
 
+def test_paths_on_a_caller_grid(pkg, dev):
+    """A device-mode batch (W = NULL) with the caller's t (rollout_heston_chain_kernel
+    on p.t): X is the oracle rollout of the drawn increments on that grid.  M = 17
+    is ragged against the 16-path groups, the grid differs from path to path."""
+    k, M, Ng = 3, 17, 5
+    s = corr_solver(pkg, dev, k)
+    _, dW = s.brownian(M, Ng, seed=SEED, increments=True)
+    tg = np.sort(np.random.RandomState(k).uniform(0, 1, size=(M, Ng + 1)), 1).astype(np.float32)
+    tg[:, 0] = 0.0
+    X = torch.empty(M * (Ng + 1) * s.D, device=dev)
+    s.loss_grad(torch.zeros(s.nparams, device=dev), M, Ng, xi_dev(dev, k), t=torch.from_numpy(tg).to(dev), seed=SEED,
+                X=X, loss=torch.empty(1, device=dev))
+    torch.cuda.synchronize()
+    Xr, _ = ph.heston_rollout(hc.xi_state(k), dW.cpu().numpy(), T, tgrid=tg, **hc.HESTON)
+    np.testing.assert_array_equal(X.cpu().numpy().reshape(M, Ng + 1, 2 * k), Xr)
+    assert not np.array_equal(Xr, ph.heston_rollout(hc.xi_state(k), dW.cpu().numpy(), T, **hc.HESTON)[0])   # the grid is felt
+
+
 # ------------------------------------------------------------------ 3. identity and clearing
 @pytest.mark.parametrize("k", [3, 50])
 def test_identity_factor_and_clearing(pkg, dev, k):

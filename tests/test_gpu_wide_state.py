@@ -315,3 +315,27 @@ def test_correlated_device_mode_wide(pkg, dev, D):
     s.set_corr(None)
     _, dWu = s.brownian(24, N, seed=4, increments=True)
     np.testing.assert_allclose(dWu.cpu().numpy(), ph.increments(4, 0, 0, 24, N, D, T), rtol=2e-6, atol=2e-6)
+
+
+def test_correlated_device_mode_wide_on_a_caller_grid(pkg, dev):
+    """A device-mode batch (W = NULL) with the caller's t on the wide correlated
+    path (the Euler chains of rollout_chain_kernel on p.t): X is the oracle
+    rollout of the drawn increments on that grid.  M = 17 is ragged against the
+    16-path groups, the grid differs from path to path."""
+    D, M, N = 130, 17, 5
+    rs = np.random.RandomState(D)
+    A = rs.normal(size=(D, D))
+    C = A @ A.T + D * np.eye(D)
+    d = np.sqrt(np.diag(C))
+    s = pkg.NativeSolver("NAIS-Net", [D + 1, 16, 16, 16, 16, 1], "Sine", spec_for(pkg, "basket", D), T, dev)
+    s.set_corr(np.linalg.cholesky(C / np.outer(d, d)))
+    _, dW = s.brownian(M, N, seed=4, increments=True)
+    tg = np.sort(rs.uniform(0, 1, size=(M, N + 1)), 1).astype(np.float32)
+    tg[:, 0] = 0.0
+    X = torch.empty(M * (N + 1) * D, device=dev)
+    s.loss_grad(torch.zeros(s.nparams, device=dev), M, N, torch.ones(D, device=dev), t=torch.from_numpy(tg).to(dev),
+                seed=4, X=X, loss=torch.empty(1, device=dev))
+    torch.cuda.synchronize()
+    ref = ph.rollout(np.ones((1, D)), dW.cpu().numpy(), T, 0.05, 0.2, 0.0, tgrid=tg)
+    np.testing.assert_array_equal(X.cpu().numpy().reshape(M, N + 1, D), ref)
+    assert not np.array_equal(ref, ph.rollout(np.ones((1, D)), dW.cpu().numpy(), T, 0.05, 0.2, 0.0))   # the grid is felt

@@ -2,14 +2,14 @@
 tree's, in one session on one GPU (profiles/heston2_bench_ab.json,
 profiles/heston_corr_bench_ab.json have this format).  Needs a GPU.
 
-    python tools/bench_ab.py PARENT_LIB OUT.json [PARENT_COMMIT] [REPEATS]
+    python tools/bench_ab.py PARENT_LIB OUT.json [PARENT_COMMIT] [REPEATS] [WORKLOADS]
 
 PARENT_LIB is a libdbsde.so built from the parent commit; each run selects its
-library through DBSDE_LIB (the in-tree one when unset).  Per workload (the
-headline bsb, and --workload heston): `python bench.py --gpus 1 --steps 50
---warmup 10`, parent and this change alternating REPEATS (5) times, the order
-inside each pair alternating too; then --dump-outputs of both, compared
-bitwise.  Recorded: every ms/step, the medians, the parent's own spread
+library through DBSDE_LIB (the in-tree one when unset).  Per workload (WORKLOADS,
+comma-separated names of bench.py's --workload; default bsb,heston): `python
+bench.py --gpus 1 --steps 50 --warmup 10`, parent and this change alternating
+REPEATS (5) times, the order inside each pair alternating too; then
+--dump-outputs of both, compared bitwise.  Recorded: every ms/step, the medians, the parent's own spread
 (max - min) and whether the medians differ by less than it."""
 import json
 import os
@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARENT_LIB, OUT = os.path.abspath(sys.argv[1]), sys.argv[2]
 PARENT_COMMIT = sys.argv[3] if len(sys.argv) > 3 else None
 REPEATS = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+WORKLOADS = tuple(sys.argv[5].split(",")) if len(sys.argv) > 5 else ("bsb", "heston")
 DUMPS = os.path.join(ROOT, "bench_out", "bench_ab")
 
 
@@ -42,11 +43,11 @@ def bench(arm, workload, dump=None):
     return json.loads(r.stdout.strip().split("\n")[-1])
 
 
-res = {"what": "python bench.py --gpus 1 --steps 50 --warmup 10 (the headline bsb, and --workload heston) on the parent "
+res = {"what": f"python bench.py --gpus 1 --steps 50 --warmup 10 (--workload {', '.join(WORKLOADS)}) on the parent "
                f"commit's library and on this change's, alternating {REPEATS} times each in one session on one MI355X "
                "(the order inside each pair alternates too); then --dump-outputs of both",
        "parent_commit": PARENT_COMMIT, "workloads": {}}
-for workload in ("bsb", "heston"):
+for workload in WORKLOADS:
     runs = {"parent": [], "this": []}
     for i in range(REPEATS):
         for arm in (("parent", "this") if i % 2 == 0 else ("this", "parent")):
