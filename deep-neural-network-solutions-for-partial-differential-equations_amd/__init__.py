@@ -15,8 +15,8 @@ from .deepbsde import BlackScholesBarenblatt, u_exact
 from .fbsnn import FBSNN, PredictionGenerator
 from .problems import (BasketCallOption, BSPDETestCase, CallOption, CallOption1D, HamiltonJacobiBellman, HestonFBSNN,
                        HestonTwoFactorFBSNN)
-from .solver import NativeSolver, ProblemSpec, exact, hjb_mc, mc_value
+from .solver import NativeSolver, ProblemSpec, exact, free_call_profile, hjb_mc, mc_value
 
 __all__ = ["FBSNN", "PredictionGenerator", "BlackScholesBarenblatt", "u_exact", "CallOption", "CallOption1D",
            "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman", "HestonFBSNN", "HestonTwoFactorFBSNN",
-           "NativeSolver", "ProblemSpec", "exact", "hjb_mc", "mc_value", "_lib"]
+           "NativeSolver", "ProblemSpec", "exact", "free_call_profile", "hjb_mc", "mc_value", "_lib"]

@@ -18,6 +18,7 @@ MODES = {"FC": 0, "NAIS-Net": 1, "Resnet": 2, "Naisnet": 3}
 ACTIVATIONS = {"Sine": 0, "ReLU": 1, "Tanh": 2}
 G_KINDS = {"sumsq": 0, "call_sum": 1, "call_mean": 2, "log": 3, "smooth_call": 4}
 PROBLEM_KINDS = {"diag": 0, "heston": 1, "heston2": 2}
+PROB_HESTON_CORR = 3   # dbsde_mc_value's kind for "heston" with a factor between the assets: not a context kind
 OPTIMIZERS = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3, "Adagrad": 4, "Adamax": 5, "Adadelta": 6, "ASGD": 7}
 EXACT_KINDS = {"bsb": 0, "bs_call": 1, "basket_avg": 2, "basket_mean": 3, "heston": 4}
 ABI_VERSION = 3

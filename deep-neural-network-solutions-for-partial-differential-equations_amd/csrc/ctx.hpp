@@ -239,6 +239,7 @@ int dalloc(dbsde_ctx* c, void** p, size_t bytes);
 int ensure_rows(dbsde_ctx* c, int Rp, int N);
 hipEvent_t get_event(dbsde_ctx* c);
 int prof_id(dbsde_ctx* c, const std::string& name);
+dbsde_ctx* free_call_ctx();   // the profiling store of dbsde_profile_*(NULL, ...)
 
 #define HIPC(ctx, expr)                                                                        \
   do {                                                                                          \

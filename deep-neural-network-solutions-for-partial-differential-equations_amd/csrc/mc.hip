@@ -51,18 +51,35 @@
 // lower triangle only) and returns through LDS to the (k, d) threads: one
 // product per four steps, shared by the tile's points and scaled by each
 // point's sqdt afterwards.
-// Nothing per path goes to HBM.
+// Nothing per path goes to HBM, but for the increments of the
+// correlated Heston (DBSDE_PROB_HESTON_CORR, L [k, k] between the assets'
+// Brownian motions), two passes at every k <= 511, as the correlated Heston
+// rollout (paths.hpp): pass 1 is that rollout's increment GEMM
+// rollout_corrw_kernel over samples as paths (mc_corr_increments, rollout.hip)
+// writing the UNSCALED L z [samples, n_steps, k] to a workspace -- the points of
+// a call share them and scale by their own sqdt, as CORR does; pass 2 is
+// mc_kernel<MC_HESTON, false, true>: kind HESTON's path with the four normals of
+// a Philox block loaded from column d of the sample's workspace rows (adjacent
+// d coalesce) instead of drawn.  The workspace is bounded (DBSDE_MC_WS_MB, read
+// per call): the sample chunks (grid.y) run in groups whose increments fit it,
+// pass 1 then pass 2 on the group's grid.y sub-range (McArgs::ch0), a chunk
+// larger than the bound as a group of its own; mc_final_kernel runs once after
+// the last group.  per and nch do not depend on the grouping, and a chunk's
+// partials do not depend on its group, so neither do the bits of the result.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <string>
 
-#include "../../include/dbsde.h"
+#define DBSDE_DEVICE_HELPERS_ONLY
+#include "ctx.hpp"
 #include "philox.hpp"
 #include "sde.hpp"
 
-struct dbsde_ctx;
-int fail(dbsde_ctx* c, int code, const std::string& msg);   // net.hip
+// rollout.hip
+int mc_corr_increments(dbsde_ctx* pc, hipStream_t s, const float* Lt, int k, int n_steps, unsigned long long seed,
+                       unsigned long long offset, long long k0, long long count, float* ws);
 
 namespace dbsde {
 
@@ -73,6 +90,8 @@ constexpr int MC_CHUNKS = 256;     // sample chunks (grid.y) at most
 constexpr int MC_DMAX = 4096;
 constexpr int MC_NBMAX = 128;      // correlated: L in LDS
 constexpr int MC_LPACK = MC_NBMAX * (MC_NBMAX + 1) / 2;
+constexpr int MC_HCMAX = 511;      // correlated Heston: dbsde_set_corr's limit for Heston contexts
+constexpr int MC_WS_MB = 1024;     // correlated Heston: default workspace bound (DBSDE_MC_WS_MB)
 constexpr int MC_ZMAX = 2048;       // correlated: floats of the Z (and C) tile, nd x (4 S padded to 16) <= 2048
 enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2, MC_HESTON2 = 3 };
 
@@ -95,6 +114,11 @@ struct McArgs {
   float* sqdt;                     // [Ppad]
   float* Lp;                       // packed lower triangle of L^T: row j holds L[d][j], d = j .. nd - 1
   double* part;                    // [P, nch, W]
+  // correlated Heston (mc_kernel WS)
+  float* Lt;                       // L^T [nd][nd], zero where L's upper triangle is (rollout_corrw_kernel's operand)
+  const float* ws;                 // the group's unscaled increments L z [samples, n_steps, nd]
+  long long ws_k0;                 // its first sample
+  int ch0;                         // its first chunk: workgroup row blockIdx.y runs chunk ch0 + blockIdx.y
 };
 
 __device__ __forceinline__ int mc_lp_off(int j, int nd) { return j * nd - (j * (j - 1)) / 2; }
@@ -121,7 +145,8 @@ __global__ void __launch_bounds__(256) mc_grid_kernel(McArgs a) {
   if (a.L)
     for (int e = gid; e < a.nd * a.nd; e += gridDim.x * 256) {
       const int d = e / a.nd, j = e - d * a.nd;
-      if (j <= d) a.Lp[mc_lp_off(j, a.nd) + d - j] = a.L[e];
+      if (a.Lp && j <= d) a.Lp[mc_lp_off(j, a.nd) + d - j] = a.L[e];
+      if (a.Lt) a.Lt[(size_t)j * a.nd + d] = j <= d ? a.L[e] : 0.f;
     }
 }
 
@@ -155,14 +180,20 @@ __device__ __forceinline__ void mc_payoff(int g_kind, double s, double cols, dou
 // points.  DIAG / CORR: X the state, V the tangent J (DELTA).  HESTON / HESTON2: X = S_d,
 // V = v_d.  s: the thread's sample slot, act: the thread owns a (sample,
 // coordinate) pair.  Every thread of the workgroup calls this (CORR has
-// barriers inside).
-template <int KIND, bool DELTA>
+// barriers inside).  WS (correlated Heston): wz is column d of the sample's
+// workspace rows [n_steps][nd], null for a thread without a live pair.
+template <int KIND, bool DELTA, bool WS>
 __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int s, bool act, int p0,
                                         const float (&sq)[MC_PT], float (&X)[MC_PT], float (&V)[MC_PT], float* zs,
-                                        const float* Ls) {
+                                        const float* Ls, const float* wz) {
   for (int n0 = 0; n0 < a.n_steps; n0 += 4) {
     float z[4];
-    philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)d, z);
+    if constexpr (WS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) z[i] = (wz && n0 + i < a.n_steps) ? wz[(size_t)(n0 + i) * a.nd] : 0.f;
+    } else {
+      philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)d, z);
+    }
     float zv[4] = {0.f, 0.f, 0.f, 0.f};   // two-factor Heston: the normals of W^v_d, coordinate nd + d
     if constexpr (KIND == MC_HESTON2) philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)(a.nd + d), zv);
     if constexpr (KIND == MC_CORR) {
@@ -238,8 +269,9 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
   if constexpr (KIND == MC_CORR) __syncthreads();   // the C tile shares LDS with what the caller writes next
 }
 
-template <int KIND, bool DELTA>
+template <int KIND, bool DELTA, bool WS = false>
 __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
+  static_assert(!WS || (KIND == MC_HESTON && !DELTA), "the workspace increments are the correlated Heston's");
   __shared__ __attribute__((aligned(16))) double fred[MC_PT * MC_THREADS];
   __shared__ float gpl[MC_THREADS];
   // correlated: Z and C of mc_path share fred's 16 KB (fred is written only after a
@@ -248,7 +280,9 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
   float* zs = reinterpret_cast<float*>(fred);
   __shared__ float Ls[KIND == MC_CORR ? MC_LPACK : 1];
   const int tid = threadIdx.x;
-  const int p0 = blockIdx.x * MC_PT, ch = blockIdx.y;
+  int ch = blockIdx.y;
+  if constexpr (WS) ch += a.ch0;
+  const int p0 = blockIdx.x * MC_PT;
   const int nd = a.nd, S = a.S, nj = a.nj;
   if constexpr (KIND == MC_CORR)
     for (int e = tid; e < nd * (nd + 1) / 2; e += MC_THREADS) Ls[e] = a.Lp[e];   // read after mc_path's first barrier
@@ -289,7 +323,10 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
         X[i] = a.x[(size_t)pc[i] * a.D + dd];
         V[i] = (KIND == MC_HESTON || KIND == MC_HESTON2) ? a.x[(size_t)pc[i] * a.D + nd + dd] : 1.f;
       }
-      mc_path<KIND, DELTA>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls);
+      const float* wz = nullptr;
+      if constexpr (WS)
+        if (dl) wz = a.ws + (size_t)(kk - a.ws_k0) * a.n_steps * nd + dd;
+      mc_path<KIND, DELTA, WS>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls, wz);
       if (dl) {
 #pragma unroll
         for (int i = 0; i < MC_PT; ++i) {
@@ -326,7 +363,7 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
             X[i] = a.x[(size_t)pc[i] * a.D + dd];
             V[i] = 1.f;
           }
-          mc_path<KIND, DELTA>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls);
+          mc_path<KIND, DELTA, WS>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls, nullptr);
         }
         if (!dl) continue;
 #pragma unroll
@@ -435,18 +472,24 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (P < 1 || D < 1 || n_steps < 1 || mc < 1) return bad("P, D, n_steps and mc must be >= 1");
   if (mc > (1LL << 32)) return bad("mc must be <= 2^32 (the sample index is a 32-bit counter word)");
   if (D > MC_DMAX) return bad("D must be <= 4096");
-  if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2)
+  if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2 &&
+      prob->kind != DBSDE_PROB_HESTON_CORR)
     return bad("unknown problem kind");
   if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_CALL) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
     return bad("phi_zz != 0 is not a linear problem (no Feynman-Kac expectation); the HJB comparator is dbsde_hjb_mc");
   const bool heston2 = prob->kind == DBSDE_PROB_HESTON2;   // the same state and the same refusals
-  const bool heston = prob->kind == DBSDE_PROB_HESTON || heston2;
+  const bool hcorr = prob->kind == DBSDE_PROB_HESTON_CORR;   // kind HESTON's process, its assets correlated by L
+  const bool heston = prob->kind == DBSDE_PROB_HESTON || heston2 || hcorr;
+  if (hcorr && !L) return bad("DBSDE_PROB_HESTON_CORR needs the factor L [k, k] (independent assets: DBSDE_PROB_HESTON)");
   if (heston && (D & 1)) return bad("the Heston state [S_1..S_k, v_1..v_k] needs an even D");
-  if (heston && L) return bad("L applies to DIAG problems only");
+  if (heston && !hcorr && L)
+    return bad("L applies to DIAG problems only (correlated Heston assets: DBSDE_PROB_HESTON_CORR)");
   if (heston && delta)
     return bad("no pathwise delta for Heston (the S and v tangents couple); bump and reprice on the same draws");
-  if (L && D > MC_NBMAX) return bad("L needs D <= 128");
+  if (hcorr && D / 2 > MC_HCMAX) return bad("correlated Heston needs k = D / 2 <= 511");
+  if (hcorr && (n_steps + 3) / 4 > 65535) return bad("correlated Heston needs n_steps <= 262140");
+  if (!hcorr && L && D > MC_NBMAX) return bad("L needs D <= 128");
 
   McArgs a{};
   a.D = D;
@@ -488,18 +531,51 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   const size_t b_part = up256((size_t)P * a.nch * a.W * sizeof(double));
   const size_t b_dtab = up256((size_t)n_steps * a.Ppad * sizeof(float));
   const size_t b_sq = up256((size_t)a.Ppad * sizeof(float));
-  const size_t b_lp = L ? up256((size_t)MC_LPACK * sizeof(float)) : 0;
+  const size_t b_lp = hcorr ? up256((size_t)a.nd * a.nd * sizeof(float)) : L ? up256((size_t)MC_LPACK * sizeof(float)) : 0;
+  // correlated Heston: the chunks of a group and its workspace
+  int cg = a.nch;
+  size_t b_ws = 0;
+  if (hcorr) {
+    const char* e = getenv("DBSDE_MC_WS_MB");
+    const double mb = e ? atof(e) : 0.0;   // megabytes, fractions allowed; unset or not positive: the default
+    const double chunk = (double)a.per * n_steps * a.nd * sizeof(float);
+    const double fit = (mb > 0.0 ? mb : (double)MC_WS_MB) * 1048576.0 / chunk;
+    cg = fit < 1.0 ? 1 : (fit < (double)a.nch ? (int)fit : a.nch);
+    const long long rows = std::min<long long>((long long)cg * a.per, mc);
+    b_ws = up256((size_t)rows * n_steps * a.nd * sizeof(float));
+  }
   char* buf = nullptr;
-  if (hipMallocAsync((void**)&buf, b_part + b_dtab + b_sq + b_lp, st) != hipSuccess)
+  if (hipMallocAsync((void**)&buf, b_part + b_dtab + b_sq + b_lp + b_ws, st) != hipSuccess)
     return fail(nullptr, DBSDE_ENOMEM, "dbsde_mc_value: hipMallocAsync failed");
   a.part = (double*)buf;
   a.dtab = (float*)(buf + b_part);
   a.sqdt = (float*)(buf + b_part + b_dtab);
-  a.Lp = L ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
+  a.Lp = L && !hcorr ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
+  a.Lt = hcorr ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
 
   mc_grid_kernel<<<(a.Ppad + 255) / 256, 256, 0, st>>>(a);
   const dim3 grid(tiles, a.nch);
-  if (heston2)
+  if (hcorr) {
+    dbsde_ctx* pc = free_call_ctx();
+    if (pc->prof) pc->stream = st;   // what dbsde_profile_read(NULL, ...) synchronises
+    a.ws = (const float*)(buf + b_part + b_dtab + b_sq + b_lp);
+    int rc = DBSDE_OK;
+    for (int c0 = 0; c0 < a.nch && rc == DBSDE_OK; c0 += cg) {
+      const int nc = std::min(cg, a.nch - c0);
+      a.ch0 = c0;
+      a.ws_k0 = (long long)c0 * a.per;
+      const long long count = std::min<long long>((long long)nc * a.per, mc - a.ws_k0);
+      rc = mc_corr_increments(pc, st, a.Lt, a.nd, n_steps, seed, offset, a.ws_k0, count, (float*)a.ws);
+      if (rc == DBSDE_OK)
+        rc = run(pc, st, "mc_heston_corr_paths", 0.0, 4.0 * (double)count * n_steps * a.nd * tiles, [&]() {
+          mc_kernel<MC_HESTON, false, true><<<dim3(tiles, nc), MC_THREADS, 0, st>>>(a);
+        });
+    }
+    if (rc != DBSDE_OK) {
+      (void)hipFreeAsync(buf, st);
+      return rc;
+    }
+  } else if (heston2)
     mc_kernel<MC_HESTON2, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (heston)
     mc_kernel<MC_HESTON, false><<<grid, MC_THREADS, 0, st>>>(a);

@@ -138,6 +138,14 @@ hipEvent_t get_event(dbsde_ctx* c) {
   return e;
 }
 
+// the profiling store of the calls that take no context (dbsde_mc_value): a
+// context that is never created on a device -- only its profiling members and
+// its stream are used -- made at first use and kept for the process
+dbsde_ctx* free_call_ctx() {
+  static dbsde_ctx* const c = new dbsde_ctx();
+  return c;
+}
+
 int prof_id(dbsde_ctx* c, const std::string& name) {
   auto it = c->agg_idx.find(name);
   if (it != c->agg_idx.end()) return it->second;
@@ -269,6 +277,10 @@ int build_net(dbsde_ctx* c) {
   c->x3chain = c->tnx3 && !c->fused;
   // problem kind: Brownian dimension, g columns, u clamp
   const dbsde_problem& pr = g.problem;
+  if (pr.kind == DBSDE_PROB_HESTON_CORR)
+    return fail(c, DBSDE_EINVAL,
+                "DBSDE_PROB_HESTON_CORR is dbsde_mc_value's kind: a context takes kind DBSDE_PROB_HESTON plus "
+                "dbsde_set_corr");
   if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON && pr.kind != DBSDE_PROB_HESTON2)
     return fail(c, DBSDE_EINVAL, "unknown problem kind");
   if (pr.g_kind < 0 || pr.g_kind > 4) return fail(c, DBSDE_EINVAL, "unknown terminal condition");
@@ -781,7 +793,7 @@ int dbsde_param_used_mask(const dbsde_ctx* c, unsigned char* mask, long long n) 
 extern "C" {
 
 int dbsde_profile_enable(dbsde_ctx* c, int enable) {
-  if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
+  if (!c) c = free_call_ctx();
   c->prof = enable != 0;
   return DBSDE_OK;
 }
@@ -805,7 +817,7 @@ static int collect(dbsde_ctx* c) {
 }
 
 int dbsde_profile_count(dbsde_ctx* c) {
-  if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
+  if (!c) c = free_call_ctx();
   int rc = collect(c);
   if (rc) return rc;
   return (int)c->agg.size();
@@ -813,7 +825,7 @@ int dbsde_profile_count(dbsde_ctx* c) {
 
 int dbsde_profile_read(dbsde_ctx* c, int idx, char* name, int name_len, double* total_ms, double* flops,
                        double* bytes, long long* launches) {
-  if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
+  if (!c) c = free_call_ctx();
   int rc = collect(c);
   if (rc) return rc;
   if (idx < 0 || idx >= (int)c->agg.size()) return fail(c, DBSDE_EINVAL, "profile index out of range");
@@ -830,7 +842,7 @@ int dbsde_profile_read(dbsde_ctx* c, int idx, char* name, int name_len, double* 
 }
 
 int dbsde_profile_reset(dbsde_ctx* c) {
-  if (!c) return fail(nullptr, DBSDE_EINVAL, "ctx is NULL");
+  if (!c) c = free_call_ctx();
   int rc = collect(c);
   if (rc) return rc;
   for (auto& a : c->agg) {

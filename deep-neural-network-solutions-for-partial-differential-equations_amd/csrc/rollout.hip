@@ -38,6 +38,38 @@ int validate_batch(dbsde_ctx* c, const dbsde_batch* b) {
   return DBSDE_OK;
 }
 
+// The increment pass of dbsde_mc_value's correlated Heston (mc.hip): the
+// UNSCALED L z of samples [k0, k0 + count) as paths, ws [count, n_steps, k].
+// T = N makes the kernel's own sqrtf(T / N) exactly 1; each point of the call
+// applies its sqrt(dt_p) afterwards.  rollout_corrw_kernel counts (path, dim)
+// in ints, so the samples go in slices of at most 2^31 / k (a multiple of
+// CW_PATHS) per launch.  pc: the profiling store of the context-free calls.
+int mc_corr_increments(dbsde_ctx* pc, hipStream_t s, const float* Lt, int k, int n_steps, unsigned long long seed,
+                       unsigned long long offset, long long k0, long long count, float* ws) {
+  if (k < 1 || k > CW_OB * 8 * 16 / 2 || n_steps < 1 || count < 1)
+    return fail(pc, DBSDE_EINVAL, "internal: correlated Heston increment geometry");
+  const long long slice = (0x7fffffffLL / k) / CW_PATHS * CW_PATHS;
+  for (long long m0 = 0; m0 < count; m0 += slice) {
+    RolloutArgs ra{};
+    ra.M = (int)std::min(slice, count - m0);
+    ra.N = n_steps;
+    ra.D = 2 * k;
+    ra.nb = k;
+    ra.T = (float)n_steps;
+    ra.seed = seed;
+    ra.offset = offset;
+    ra.path0 = k0 + m0;
+    ra.Lt = Lt;
+    ra.out = PATH_FETCH_DW;
+    ra.W_out = ws + (size_t)m0 * n_steps * k;
+    const dim3 g((ra.M + CW_PATHS - 1) / CW_PATHS, (n_steps + 3) / 4);
+    const double steps = (double)ra.M * n_steps;
+    RUN(pc, s, "corr_increments", 2.0 * steps * k * k / 2, 4.0 * steps * k,
+        rollout_corrw_kernel<<<g, CW_THREADS, 0, s>>>(ra));
+  }
+  return DBSDE_OK;
+}
+
 namespace {
 
 // batch b's paths into the rows of (xin, sdw)

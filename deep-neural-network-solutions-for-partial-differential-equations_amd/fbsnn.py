@@ -827,15 +827,15 @@ class FBSNN(ABC):
         (t [P], X [P, D]): the Feynman-Kac expectation E[exp(-phi_r tau) g(X_T)]
         under the problem's own Euler scheme (solver.mc_value, dbsde_mc_value),
         with this object's problem_spec(), T, strike and -- for a correlated
-        diagonal problem -- the Cholesky factor its device mode uses.  n_steps
+        object, diagonal or Heston -- the Cholesky factor its device mode uses
+        (Heston: [k, k] between the assets' Brownian motions).  n_steps
         defaults to self.N.  Every point sees the same Philox draws.  Returns
         (value [P, 1], stderr [P, 1], delta [P, D] or None).  Linear problems
         only: phi_zz != 0 (HJB) raises ValueError (use hjb_mc), and so does a
         problem running its own coefficient methods (the generic path), whose
-        SDE the kernel does not know.  A Heston object's comparator simulates
-        INDEPENDENT assets even when the object is correlated (dbsde_mc_value
-        takes no factor for Heston): its value is then not the trained
-        network's target."""
+        SDE the kernel does not know.  A correlated Heston object's comparator
+        runs the correlated process its rollouts run (the same draws, the same
+        increment product), so its value is the trained network's target."""
         if not self.native_coefficients:
             raise ValueError(f"{type(self).__name__} runs its own coefficient methods ({self.generic_reason}); "
                              "mc_value needs a problem_spec() the native step runs")
@@ -844,7 +844,7 @@ class FBSNN(ABC):
             raise ValueError(f"{type(self).__name__} is not linear (phi_zz != 0): its comparator is hjb_mc")
         X = self._mc_state(X)
         t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1).contiguous()
-        L = self._L if (self._L is not None and spec.kind == "diag") else None
+        L = self._L if (self._L is not None and spec.kind in ("diag", "heston")) else None
         return _mc_value(spec, t, X, self.T, self.N if n_steps is None else n_steps, mc=mc, seed=seed, L=L,
                          delta=delta)
 

@@ -289,8 +289,8 @@ class HestonFBSNN(FBSNN):
         together, matching calculate_greeks' all-ones cotangent: delta is the
         directional derivative along (1, .., 1) and gamma its second difference,
         each repeated over the k columns.  No u clamp is applied (the expectation
-        of a non-negative payoff needs none).  As mc_value, the comparator
-        simulates independent assets even when the object is correlated."""
+        of a non-negative payoff needs none).  As mc_value, a correlated object
+        bumps and reprices on its correlated process."""
         k = self.n_assets
         S = torch.as_tensor(np.asarray(S), dtype=torch.float32).to(self.device).reshape(-1, k)
         v = torch.as_tensor(np.asarray(v), dtype=torch.float32).to(self.device).reshape(-1, k)

@@ -379,6 +379,30 @@ class NativeSolver:
 
 
 # ---------------------------------------------------------------------- evaluators
+def free_call_profile(enable=None, reset=False):
+    """The per-launch profile of the calls that take no context (dbsde_profile_*
+    with ctx NULL): mc_value of a correlated Heston problem records its launches
+    there ("corr_increments", "mc_heston_corr_paths") while it is enabled.
+    enable: True / False switches recording; reset: zero the sums.  Returns
+    {name: dict(ms, flops, bytes, launches)} as NativeSolver.profile_read."""
+    lib = _lib.load()
+    if enable is not None:
+        _lib.check(lib.dbsde_profile_enable(None, int(enable)))
+    if reset:
+        _lib.check(lib.dbsde_profile_reset(None))
+    n = lib.dbsde_profile_count(None)
+    if n < 0:
+        _lib.check(n)
+    out = {}
+    name = ctypes.create_string_buffer(128)
+    ms, fl, by, nl = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
+    for i in range(n):
+        _lib.check(lib.dbsde_profile_read(None, i, name, 128, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(by),
+                                          ctypes.byref(nl)))
+        out[name.value.decode()] = dict(ms=ms.value, flops=fl.value, bytes=by.value, launches=nl.value)
+    return out
+
+
 def exact(kind, t, X, T, params):
     """Device exact / comparator solutions (include/dbsde.h dbsde_exact):
     kind in {"bsb", "bs_call", "basket_avg", "basket_mean", "heston"}; t [R],
@@ -430,12 +454,25 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
     Euler scheme with drift mu_a + phi_r phi_c, on the device-mode rollout's
     Philox draws -- the same draws for every point (common random numbers).
     spec: a ProblemSpec with phi_zz == 0 (HJB: hjb_mc); t [P], X [P, D] float32
-    cuda tensors (Heston: D = 2k, [S.., v..]); L: an optional [D, D] lower
-    Cholesky factor (diag problems, D <= 128 here, although the training
-    step's set_corr takes D <= 1022).  Returns (value [P, 1], stderr
-    [P, 1], delta [P, D] or None); delta is the pathwise estimator (diag only)."""
+    cuda tensors (Heston: D = 2k, [S.., v..]); L: an optional lower Cholesky
+    factor: [D, D] for diag problems (D <= 128 here, although the training
+    step's set_corr takes D <= 1022), [k, k] between the k = D / 2 <= 511 assets'
+    Brownian motions for kind "heston" (the process of a Heston solver with
+    set_corr; sent as DBSDE_PROB_HESTON_CORR); "heston2" takes none.  Returns
+    (value [P, 1], stderr [P, 1], delta [P, D] or None); delta is the pathwise
+    estimator (diag only)."""
     if spec.phi_zz != 0:
         raise ValueError("mc_value needs a linear problem (phi_zz == 0); the HJB comparator is hjb_mc")
+    if L is not None:   # the checks that need no device
+        import numpy as np
+        L = np.ascontiguousarray(np.asarray(L.cpu() if isinstance(L, torch.Tensor) else L, dtype=np.float32))
+        if spec.kind == "heston2":
+            raise ValueError("L applies to DIAG problems and to kind 'heston' only: the two-factor Heston model has "
+                             "no correlation between assets")
+        D_ = X.numel() // max(X.shape[0], 1)
+        n = D_ // 2 if spec.kind == "heston" else D_
+        if L.shape != (n, n) or (spec.kind == "heston" and D_ % 2):
+            raise ValueError(f"L must be [{n}, {n}]" + (" (k = D / 2 assets)" if spec.kind == "heston" else ""))
     lib = _lib.load()
     X = X.reshape(X.shape[0], -1).contiguous().float()
     t = t.reshape(-1).contiguous().float()
@@ -444,15 +481,13 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
         raise ValueError("t [P] and X [P, D] must be float32 tensors on the same HIP device")
     Ld = None
     if L is not None:
-        import numpy as np
-        Ld = torch.as_tensor(np.ascontiguousarray(np.asarray(L.cpu() if isinstance(L, torch.Tensor) else L,
-                                                             dtype=np.float32))).to(X.device)
-        if tuple(Ld.shape) != (D, D):
-            raise ValueError(f"L must be [{D}, {D}]")
+        Ld = torch.as_tensor(L).to(X.device)
     value = torch.empty((P, 1), device=X.device)
     err = torch.empty((P, 1), device=X.device)
     dl = torch.empty((P, D), device=X.device) if delta else None
     prob = spec.to_c()
+    if Ld is not None and spec.kind == "heston":
+        prob.kind = _lib.PROB_HESTON_CORR
     s = torch.cuda.current_stream(X.device).cuda_stream
     _lib.check(lib.dbsde_mc_value(ctypes.byref(prob), D, float(T), _ptr(Ld), _ptr(t), _ptr(X), P, int(n_steps),
                                   int(mc), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _ptr(value),

@@ -69,6 +69,10 @@ extern "C" {
 #define DBSDE_PROB_HESTON2 2  /* the two-factor (textbook) Heston model, the same state:
                                  Brownian motions W^S_i and W^v_i per asset, correlation
                                  h_rho between the two, none between assets            */
+#define DBSDE_PROB_HESTON_CORR 3 /* dbsde_mc_value only: kind HESTON's process with the
+                                 assets' Brownian motions correlated by its L argument,
+                                 dW = sqrt(dt) (L z), L [k, k].  A context takes kind
+                                 HESTON plus dbsde_set_corr instead                    */
 
 /*
  * Problem coefficients (one FBSNN subclass = one filled struct):
@@ -97,6 +101,8 @@ extern "C" {
  *     dbsde_set_corr on such a context is DBSDE_EINVAL (no correlation between
  *     assets), dbsde_mc_value takes neither L nor delta for it, and
  *     DBSDE_EXACT_HESTON is its closed form for k = 1 and a call payoff.
+ *   kind HESTON_CORR: HESTON's fields, state and step, for dbsde_mc_value alone (the
+ *     factor is that call's L argument); dbsde_create refuses it.
  *   phi      =phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
  *   g        = g_kind over the first g_cols state columns (0 = all), strike,
  *              g_alpha (DBSDE_G_SMOOTH_CALL); the terminal |Z - grad g|^2 term
@@ -187,8 +193,9 @@ int dbsde_brownian_dim(const dbsde_ctx* ctx);
  * device-mode rollout, dbsde_prefetch, dbsde_brownian and the rank shards
  * (path0) then run on dW = L (sqrt(dt) z) -- the increment GEMM at every k,
  * followed by a per-(path, asset) Euler chain -- and dbsde_pde_residual takes
- * the columns of Sigma(x) . L.  dbsde_mc_value does not: it refuses a Heston
- * problem with a factor.
+ * the columns of Sigma(x) . L.  dbsde_mc_value simulates the same process when it
+ * is given the factor with kind DBSDE_PROB_HESTON_CORR (kind HESTON with L stays
+ * DBSDE_EINVAL there).
  * HESTON2 contexts: DBSDE_EINVAL (correlation between assets is out of scope
  * for the two-factor model; L == NULL is accepted and does nothing).
  * Any other n is DBSDE_EINVAL.
@@ -481,10 +488,19 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * per asset driving both S and v, as the training step does.  HESTON2 runs its
  * two-factor step (dbsde_problem above): sample k, asset d draws the Brownian
  * coordinates d (W^S_d) and D/2 + d (W^v_d); like HESTON it takes neither L nor
- * delta.  phi_zz != 0 (HJB) is DBSDE_EINVAL: use dbsde_hjb_mc.
+ * delta.  HESTON_CORR is HESTON with the assets' Brownian motions correlated:
+ * dW = sqrt(dt_p) (L z), z the normals HESTON draws.  The unscaled L z of a group
+ * of samples are formed once for all points by the triangular increment GEMM of
+ * the correlated Heston rollout (its draws and its summation order) into a
+ * workspace [samples, n_steps, k], and the path kernel reads them instead of
+ * drawing.  The workspace is bounded by DBSDE_MC_WS_MB megabytes (read at every
+ * call, default 1024); a call that needs more runs its sample chunks in groups,
+ * which changes no bit of the result.  With L = I the result is HESTON's, bit for
+ * bit.  phi_zz != 0 (HJB) is DBSDE_EINVAL: use dbsde_hjb_mc.
  *
- *   L       device [nb, nb] row-major lower Cholesky factor, NULL = independent
- *           increments; DIAG only, nb = D <= 128
+ *   L       device [nb, nb] row-major lower Cholesky factor (the lower triangle is
+ *           read), NULL = independent increments; DIAG: nb = D <= 128;
+ *           HESTON_CORR: required, nb = k = D / 2 <= 511
  *   t, x    device t [P], x [P, D] (Heston: D = 2k, [S_1..S_k, v_1..v_k])
  *   value   device [P]:     exp(-phi_r tau_p) mean_k g(X_T)
  *   stderr_ device [P], nullable: exp(-phi_r tau_p) std_k(g, ddof = 1) / sqrt(mc)
@@ -512,14 +528,18 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  *
  * DBSDE_EINVAL before any HIP call: NULL prob / t / x / value; P, D, n_steps
  * or mc < 1; mc > 2^32; D > 4096; Heston with an odd D, with L or with delta;
- * L with D > 128; an unknown kind or g_kind; phi_zz != 0.  Needs no context;
+ * L with D > 128; HESTON_CORR without L, with an odd D, with delta or with
+ * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0.  Needs no context;
  * the work is enqueued on hip_stream.
  */
 int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const float* L, const float* t, const float* x, int P,
                    int n_steps, long long mc, unsigned long long seed, unsigned long long offset, float* value,
                    float* stderr_, float* delta, void* hip_stream);
 
-/* Per-kernel timing with HIP events on the context stream (bench/profiling). */
+/* Per-kernel timing with HIP events on the context stream (bench/profiling).
+ * ctx == NULL addresses the process-wide store of the calls that take no
+ * context: dbsde_mc_value with kind HESTON_CORR records its launches there
+ * ("corr_increments", "mc_heston_corr_paths") while that store is enabled. */
 int dbsde_profile_enable(dbsde_ctx* ctx, int enable);
 int dbsde_profile_count(dbsde_ctx* ctx);
 int dbsde_profile_read(dbsde_ctx* ctx, int idx, char* name, int name_len, double* total_ms,
