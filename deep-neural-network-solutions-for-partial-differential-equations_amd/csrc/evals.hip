@@ -6,6 +6,8 @@
 // include/dbsde.h (dbsde_exact, dbsde_hjb_mc); no context needed.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 #include "../../include/dbsde.h"
 #include "philox.hpp"
 
@@ -29,6 +31,31 @@ __device__ __forceinline__ void bs_call(double S, double K, double tau, double r
   }
 }
 
+// Black-Scholes put, computed directly (never as call minus parity, which
+// loses a deep out-of-the-money put to cancellation): K e^{-r tau} N(-d2) -
+// S N(-d1), delta -N(-d1); the payoff and its -1 / -1/2 / 0 delta at tau <= 0
+__device__ __forceinline__ void bs_put(double S, double K, double tau, double r, double sig, double& price,
+                                       double& delta) {
+  if (tau > 0.0) {
+    const double st = sig * sqrt(tau);
+    const double d1 = (log(S / K) + (r + 0.5 * sig * sig) * tau) / st;
+    const double d2 = d1 - st;
+    price = K * exp(-r * tau) * ncdf(-d2) - S * ncdf(-d1);
+    delta = -ncdf(-d1);
+  } else {
+    price = K - S > 0.0 ? K - S : 0.0;
+    delta = S < K ? -1.0 : (S == K ? -0.5 : 0.0);
+  }
+}
+template <bool PUT>
+__device__ __forceinline__ void bs_price(double S, double K, double tau, double r, double sig, double& price,
+                                         double& delta) {
+  if constexpr (PUT)
+    bs_put(S, K, tau, r, sig, price, delta);
+  else
+    bs_call(S, K, tau, r, sig, price, delta);
+}
+
 struct ExactArgs {
   int kind, D;
   long long R;
@@ -39,6 +66,8 @@ struct ExactArgs {
   float* delta;
 };
 
+// PUT: a.kind holds the call kind, the option prices are the puts'
+template <bool PUT>
 __global__ void __launch_bounds__(256) exact_kernel(ExactArgs a) {
   const long long i = blockIdx.x * 256LL + threadIdx.x;
   const long long n = a.kind == DBSDE_EXACT_BS_CALL ? a.R * a.D : a.R;
@@ -52,16 +81,16 @@ __global__ void __launch_bounds__(256) exact_kernel(ExactArgs a) {
     for (int d = 0; d < a.D; ++d) s2 += (double)xr[d] * (double)xr[d];
     price = exp((a.p0 + a.p1 * a.p1) * tau) * s2;
   } else if (a.kind == DBSDE_EXACT_BS_CALL) {
-    bs_call((double)a.x[i], a.p2, tau, a.p0, a.p1, price, delta);
+    bs_price<PUT>((double)a.x[i], a.p2, tau, a.p0, a.p1, price, delta);
   } else if (a.kind == DBSDE_EXACT_BASKET_AVG) {   // call on mean(x), sigma / sqrt(D)
     double sm = 0.0;
     for (int d = 0; d < a.D; ++d) sm += (double)xr[d];
-    bs_call(sm / a.D, a.p2, tau, a.p0, a.p1 / sqrt((double)a.D), price, delta);
+    bs_price<PUT>(sm / a.D, a.p2, tau, a.p0, a.p1 / sqrt((double)a.D), price, delta);
   } else {                                     // mean of the per-asset calls
     double ps = 0.0, ds = 0.0;
     for (int d = 0; d < a.D; ++d) {
       double pc, dc;
-      bs_call((double)xr[d], a.p2, tau, a.p0, a.p1, pc, dc);
+      bs_price<PUT>((double)xr[d], a.p2, tau, a.p0, a.p1, pc, dc);
       ps += pc;
       ds += dc;
     }
@@ -159,8 +188,12 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
-// p0..p5 = r, K, kappa, theta, sigma, rho; x [R, 2] = (S, v)
-__global__ void __launch_bounds__(256) heston_call_kernel(ExactArgs a) {
+// p0..p5 = r, K, kappa, theta, sigma, rho; x [R, 2] = (S, v).  PUT: the same
+// quadrature sums I_j = pi (P_j - 1/2) enter K e^{-r tau} (1/2 - I_2 / pi) -
+// S (1/2 - I_1 / pi), delta -(1/2 - I_1 / pi): the put's own probabilities,
+// not the call minus parity.  The call instance is the code it was.
+template <bool PUT>
+__device__ __forceinline__ void heston_price(const ExactArgs& a) {
   const int lane = threadIdx.x & 63;
   const long long r = blockIdx.x * 4LL + (threadIdx.x >> 6);
   if (r >= a.R) return;   // whole waves leave together
@@ -199,10 +232,20 @@ __global__ void __launch_bounds__(256) heston_call_kernel(ExactArgs a) {
     }
     s1 = wave_sum_f64(s1);
     s2 = wave_sum_f64(s2);
-    const double P1 = 0.5 + 0.5 * hw * s1 * 0.31830988618379067154;
-    const double P2 = 0.5 + 0.5 * hw * s2 * 0.31830988618379067154;
-    price = S * P1 - K * exp(-h.r * tau) * P2;
-    delta = P1;
+    if constexpr (PUT) {
+      const double Q1 = 0.5 - 0.5 * hw * s1 * 0.31830988618379067154;
+      const double Q2 = 0.5 - 0.5 * hw * s2 * 0.31830988618379067154;
+      price = K * exp(-h.r * tau) * Q2 - S * Q1;
+      delta = -Q1;
+    } else {
+      const double P1 = 0.5 + 0.5 * hw * s1 * 0.31830988618379067154;
+      const double P2 = 0.5 + 0.5 * hw * s2 * 0.31830988618379067154;
+      price = S * P1 - K * exp(-h.r * tau) * P2;
+      delta = P1;
+    }
+  } else if constexpr (PUT) {
+    price = K - S > 0.0 ? K - S : 0.0;
+    delta = S < K ? -1.0 : (S == K ? -0.5 : 0.0);
   } else {
     price = S - K > 0.0 ? S - K : 0.0;
     delta = S > K ? 1.0 : (S == K ? 0.5 : 0.0);
@@ -211,6 +254,8 @@ __global__ void __launch_bounds__(256) heston_call_kernel(ExactArgs a) {
   a.price[r] = (float)price;
   if (a.delta) a.delta[r] = (float)delta;
 }
+__global__ void __launch_bounds__(256) heston_call_kernel(ExactArgs a) { heston_price<false>(a); }
+__global__ void __launch_bounds__(256) heston_put_kernel(ExactArgs a) { heston_price<true>(a); }
 
 // HJB Monte-Carlo: block (p, c) sums exp(-g(x_p + s_p z_k)) = 1 / (1/2 + |y|^2/2)
 // over its share of the samples k; normals z_k[4 q + j] = normal4 of counter
@@ -271,8 +316,18 @@ extern "C" {
 
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* stream) {
-  if (kind < DBSDE_EXACT_BSB || kind > DBSDE_EXACT_HESTON || !t || !x || !params || !price || R < 1 || D < 1)
+  if (kind < DBSDE_EXACT_BSB || kind > DBSDE_EXACT_HESTON_PUT || !t || !x || !params || !price || R < 1 || D < 1)
     return DBSDE_EINVAL;
+  // the kernels read and write whole floats: an address that is no multiple of
+  // sizeof(float) (sizeof(double) for params) cannot be such a buffer, and is
+  // refused here rather than handed to a launch
+  auto misaligned = [](const void* q, size_t a) { return ((uintptr_t)q & (a - 1)) != 0; };
+  if (misaligned(t, sizeof(float)) || misaligned(x, sizeof(float)) || misaligned(price, sizeof(float)) ||
+      misaligned(delta, sizeof(float)) || misaligned(params, sizeof(double)))
+    return DBSDE_EINVAL;
+  // a put runs its call counterpart's shapes and parameters
+  const bool put = kind >= DBSDE_EXACT_BS_PUT;
+  if (put) kind -= DBSDE_EXACT_BS_PUT - DBSDE_EXACT_BS_CALL;
   if (kind == DBSDE_EXACT_HESTON && D != 2) return DBSDE_EINVAL;   // x = (S, v): one asset
   ExactArgs a{};
   a.kind = kind;
@@ -291,11 +346,17 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
     a.p4 = params[4];
     a.p5 = params[5];
     if ((R + 3) / 4 > 0x7fffffffLL) return DBSDE_EINVAL;
-    heston_call_kernel<<<(unsigned)((R + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
+    if (put)
+      heston_put_kernel<<<(unsigned)((R + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
+    else
+      heston_call_kernel<<<(unsigned)((R + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
     return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
   }
   const long long n = kind == DBSDE_EXACT_BS_CALL ? R * D : R;
-  exact_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
+  if (put)
+    exact_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
+  else
+    exact_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
   return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
 }
 

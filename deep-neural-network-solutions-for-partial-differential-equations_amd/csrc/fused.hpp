@@ -19,6 +19,7 @@ struct CotanParams {
   const float* rowsum;      // [Rp, 8]   [s_zs, s_xz, s_zz, s_x, s_xx, z_1, u-mask, 0]
   const float* q3S;         // [N] or null
   float phi_r, phi_c, phi_zz, strike, g_alpha;
+  float gsign;              // -1: put (g_kind holds the call kind, terminal_kind)
   int g_kind;
   // net_u VJP (dbsde_net_u_vjp): caller cotangents instead of the BSDE
   // residual ones -- ubar from ext_ub [Rp], zbar from the sdw rows
@@ -161,7 +162,7 @@ __device__ __forceinline__ RowCotan row_cotan(const CotanParams& p, int r) {
   c.term = term;
   c.mask = a1[2];
   if (term) {
-    c.res = y - terminal_g(p.g_kind, a0[3], a1[0], p.gcols, p.strike, p.g_alpha, c.gsc);
+    c.res = y - terminal_g(p.g_kind, a0[3], a1[0], p.gcols, p.strike, p.g_alpha, p.gsign, c.gsc);
     c.ub = 2.f * c.res;
     c.gA = p.g_kind == 0 ? 2.f : (p.g_kind == 3 ? c.gsc : 0.f);
     c.gB = (p.g_kind == 0 || p.g_kind == 3) ? 0.f : c.gsc;
@@ -278,7 +279,7 @@ __global__ void __launch_bounds__(256) zrow_cotan_kernel(ZRowArgs a) {
       c.res = step_residual(p, rs0, rs1, y, p.u[r + 1], c.dt, c.q3s);
       c.coefY = -2.f * c.res;
     } else {
-      c.res = y - terminal_g(p.g_kind, rs0[3], rs1[0], p.gcols, p.strike, p.g_alpha, c.gsc);
+      c.res = y - terminal_g(p.g_kind, rs0[3], rs1[0], p.gcols, p.strike, p.g_alpha, p.gsign, c.gsc);
       c.gA = p.g_kind == 0 ? 2.f : (p.g_kind == 3 ? c.gsc : 0.f);
       c.gB = (p.g_kind == 0 || p.g_kind == 3) ? 0.f : c.gsc;
     }

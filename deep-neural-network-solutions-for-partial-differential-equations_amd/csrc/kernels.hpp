@@ -88,14 +88,22 @@ __device__ __forceinline__ floatx4 mfma4(float a, float b, floatx4 c) {
 //   3 log     g = log(1/2 + |x|^2/2)        dg = x gsc        (hjb_implement.py:597-598)
 //   4 smooth  g = a / (1 + e^{-alpha a}), a = mean x - K      (heston_dnnpde.py:551-556)
 // torch.maximum splits the gradient 1/2 : 1/2 at a tie, so gsc = 1/2 there.
+// The puts (DBSDE_G_PUT_SUM / PUT_MEAN / SMOOTH_PUT) arrive here as kinds
+// 1 / 2 / 4 with gsign = -1 (terminal_kind below): the moneyness and the
+// gradient scale change sign and nothing else does.  gsign = 1 multiplies
+// exactly, so the calls keep their bits.
 // --------------------------------------------------------------------------
+__host__ __device__ inline int terminal_kind(int g_kind, float& gsign) {
+  gsign = g_kind >= 5 ? -1.f : 1.f;
+  return g_kind == 5 ? 1 : (g_kind == 6 ? 2 : (g_kind == 7 ? 4 : g_kind));
+}
 __device__ __forceinline__ float terminal_g(int kind, float s_x, float s_xx, int G, float strike, float alpha,
-                                            float& gsc) {
+                                            float gsign, float& gsc) {
   gsc = 0.f;
   if (kind == 0) return s_xx;
   if (kind == 1 || kind == 2) {
-    const float v = kind == 1 ? s_x - strike : s_x / (float)G - strike;
-    const float sc = kind == 1 ? 1.f : 1.f / (float)G;
+    const float v = gsign * (kind == 1 ? s_x - strike : s_x / (float)G - strike);
+    const float sc = gsign * (kind == 1 ? 1.f : 1.f / (float)G);
     gsc = v > 0.f ? sc : (v == 0.f ? 0.5f * sc : 0.f);
     return v > 0.f ? v : 0.f;
   }
@@ -104,10 +112,10 @@ __device__ __forceinline__ float terminal_g(int kind, float s_x, float s_xx, int
     gsc = 1.f / q;
     return logf(q);
   }
-  const float a = s_x / (float)G - strike;
+  const float a = gsign * (s_x / (float)G - strike);
   const float e = expf(-alpha * a);
   const float den = 1.f + e;
-  gsc = (1.f / den + a * alpha * e / (den * den)) / (float)G;
+  gsc = gsign * ((1.f / den + a * alpha * e / (den * den)) / (float)G);
   return a / den;
 }
 __device__ __forceinline__ float terminal_dg(int kind, float x, float gsc) {
@@ -159,6 +167,7 @@ struct ChainArgs {
   const float* q3S;   // [N] or null
   const float* umask; // [Rp] u-clamp gradient mask (heston_dnnpde.py:568) or null
   float phi_r, phi_c, phi_zz, strike, g_alpha;
+  float gsign;        // -1: put (g_kind holds the call kind, terminal_kind)
   int g_kind, gcols;
   float* zbar;        // [Rp, ldx]
   float* rres;        // [Rp]
@@ -310,7 +319,7 @@ __global__ void __launch_bounds__(256) chain_gemm_kernel(ChainArgs p) {
           lossv = res * res;
           coefY = -2.f * res;
         } else {
-          const float g = terminal_g(p.g_kind, s_x, s_xx, G, p.strike, p.g_alpha, gsc);
+          const float g = terminal_g(p.g_kind, s_x, s_xx, G, p.strike, p.g_alpha, p.gsign, gsc);
           res = y - g;
           lossv = res * res;
         }

@@ -154,7 +154,7 @@ __device__ __forceinline__ bool mc_squares(int g_kind) { return g_kind == DBSDE_
 
 // g and dg/d(sum) from the sum of the payoff terms (X or X^2) of a sample;
 // dg/dX_d = gp * (2 X_d or 1).  The call payoffs use 1/2 at a == 0, as bs_call
-// (evals.hip) does.
+// (evals.hip) does.  A put is its call in -a with gp negated: -1/2 at the kink.
 __device__ __forceinline__ void mc_payoff(int g_kind, double s, double cols, double K, double alpha, double& g,
                                           double& gp) {
   if (g_kind == DBSDE_G_SUMSQ) {
@@ -164,15 +164,17 @@ __device__ __forceinline__ void mc_payoff(int g_kind, double s, double cols, dou
     const double q = 0.5 + 0.5 * s;
     g = log(q);
     gp = 0.5 / q;
-  } else if (g_kind == DBSDE_G_SMOOTH_CALL) {
-    const double a = s / cols - K, sg = 1.0 / (1.0 + exp(-alpha * a));
+  } else if (g_kind == DBSDE_G_SMOOTH_CALL || g_kind == DBSDE_G_SMOOTH_PUT) {
+    const double sgn = g_kind == DBSDE_G_SMOOTH_PUT ? -1.0 : 1.0;
+    const double a = sgn * (s / cols - K), sg = 1.0 / (1.0 + exp(-alpha * a));
     g = a * sg;
-    gp = (sg + a * alpha * sg * (1.0 - sg)) / cols;
+    gp = sgn * ((sg + a * alpha * sg * (1.0 - sg)) / cols);
   } else {
-    const double c = g_kind == DBSDE_G_CALL_MEAN ? cols : 1.0;
-    const double a = s / c - K;
+    const double sgn = g_kind >= DBSDE_G_PUT_SUM ? -1.0 : 1.0;
+    const double c = (g_kind == DBSDE_G_CALL_MEAN || g_kind == DBSDE_G_PUT_MEAN) ? cols : 1.0;
+    const double a = sgn * (s / c - K);
     g = a > 0.0 ? a : 0.0;
-    gp = (a > 0.0 ? 1.0 : (a == 0.0 ? 0.5 : 0.0)) / c;
+    gp = sgn * ((a > 0.0 ? 1.0 : (a == 0.0 ? 0.5 : 0.0)) / c);
   }
 }
 
@@ -475,7 +477,7 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2 &&
       prob->kind != DBSDE_PROB_HESTON_CORR)
     return bad("unknown problem kind");
-  if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_CALL) return bad("unknown terminal condition g_kind");
+  if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_PUT) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
     return bad("phi_zz != 0 is not a linear problem (no Feynman-Kac expectation); the HJB comparator is dbsde_hjb_mc");
   const bool heston2 = prob->kind == DBSDE_PROB_HESTON2;   // the same state and the same refusals

@@ -283,7 +283,7 @@ int build_net(dbsde_ctx* c) {
                 "dbsde_set_corr");
   if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON && pr.kind != DBSDE_PROB_HESTON2)
     return fail(c, DBSDE_EINVAL, "unknown problem kind");
-  if (pr.g_kind < 0 || pr.g_kind > 4) return fail(c, DBSDE_EINVAL, "unknown terminal condition");
+  if (pr.g_kind < 0 || pr.g_kind > DBSDE_G_SMOOTH_PUT) return fail(c, DBSDE_EINVAL, "unknown terminal condition");
   c->heston = pr.kind == DBSDE_PROB_HESTON;
   c->heston2 = pr.kind == DBSDE_PROB_HESTON2;
   if ((c->heston || c->heston2) && c->D % 2 != 0)

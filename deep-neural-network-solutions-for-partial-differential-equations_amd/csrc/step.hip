@@ -443,7 +443,7 @@ CotanParams cotan_params(dbsde_ctx* c, int R, int Rp, int N1, bool q3) {
   p.phi_zz = pr.phi_zz;
   p.strike = pr.strike;
   p.g_alpha = pr.g_alpha;
-  p.g_kind = pr.g_kind;
+  p.g_kind = terminal_kind(pr.g_kind, p.gsign);
   return p;
 }
 
@@ -993,7 +993,7 @@ int loss_grad_impl(dbsde_ctx* c, const float* params, const dbsde_batch* b, floa
       a.phi_zz = pr.phi_zz;
       a.strike = pr.strike;
       a.g_alpha = pr.g_alpha;
-      a.g_kind = pr.g_kind;
+      a.g_kind = terminal_kind(pr.g_kind, a.gsign);
       a.gcols = c->gcols;
       a.zbar = c->zbar;
       a.rres = c->rres;

@@ -70,6 +70,14 @@ def spec_functions(spec, strike=None):
         if spec.g == "smooth_call":
             a = torch.mean(S, dim=1, keepdim=True) - K
             return a / (1 + torch.exp(-spec.g_alpha * a))
+        # the puts: torch.maximum, whose 1/2 : 1/2 tie gradient the device has
+        if spec.g == "put_sum":
+            return torch.maximum(K - torch.sum(S, dim=1, keepdim=True), torch.zeros((), device=X.device))
+        if spec.g == "put_mean":
+            return torch.maximum(K - torch.mean(S, dim=1, keepdim=True), torch.zeros((), device=X.device))
+        if spec.g == "smooth_put":
+            a = K - torch.mean(S, dim=1, keepdim=True)
+            return a / (1 + torch.exp(-spec.g_alpha * a))
         raise ValueError(f"unknown terminal condition {spec.g!r}")
 
     def dg(X):

@@ -6,8 +6,10 @@ so a subclass overriding one of them with other coefficients runs its own
 methods (generic.py) instead of silently training the parent's problem.
 
   CallOption            nd_BSPDE_case.py:503-539        sum-payoff call, phi = r(Y - X.Z)
+  PutOption             (no reference counterpart)      CallOption with the put payoff max(K - sum X, 0)
   CallOption1D          1d_BSPDE_case.py:510-560        1-D call, phi = 0.01 Y (Q3 broadcast)
   BasketCallOption      with_corr...py:546-596          mean-payoff basket, correlated dW
+  BasketPutOption       (no reference counterpart)      BasketCallOption with max(K - mean X, 0)
   BSPDETestCase         with_corr...py:599-616          sum X^2 payoff, mu = 0.05 X
   HamiltonJacobiBellman hjb_implement.py:590-604        phi = |Z|^2, g = log(1/2 + |X|^2/2)
   HestonFBSNN           heston_dnnpde.py:519-699        k-asset stochastic volatility
@@ -45,6 +47,17 @@ class CallOption(FBSNN):
 
     def sigma_tf(self, t, X, Y):
         return 0.20 * torch.diag_embed(X)
+
+
+class PutOption(CallOption):
+    """CallOption's problem with the put payoff max(K - sum X, 0): the same
+    dynamics, phi, strike default and train surface."""
+
+    def problem_spec(self):
+        return dataclasses.replace(super().problem_spec(), g="put_sum")
+
+    def g_tf(self, X):
+        return torch.maximum(self.strike - torch.sum(X, dim=1, keepdim=True), torch.tensor(0.0, device=X.device))
 
 
 class CallOption1D(FBSNN):
@@ -99,6 +112,17 @@ class BasketCallOption(_WithCorrTrain, FBSNN):
 
     def sigma_tf(self, t, X, Y):
         return 0.20 * torch.diag_embed(X)
+
+
+class BasketPutOption(BasketCallOption):
+    """BasketCallOption's problem with the put payoff max(K - mean X, 0): the
+    same dynamics, phi, strike default (1.0), schedule and train surface."""
+
+    def problem_spec(self):
+        return dataclasses.replace(super().problem_spec(), g="put_mean")
+
+    def g_tf(self, X):
+        return torch.maximum(self.strike - torch.mean(X, dim=1, keepdim=True), torch.tensor(0.0, device=X.device))
 
 
 class BSPDETestCase(_WithCorrTrain, FBSNN):
@@ -160,7 +184,8 @@ class HestonFBSNN(FBSNN):
     of each asset are clamped to [-100, 100] (:591, :605); u = max(net, 0)
     (:568); phi = 0.05 Y; the terminal payoff is the call on mean S (the
     reference's max(S - 1, 0) at k = 1, or its sigmoid-smoothed "continuous"
-    variant, :546-558) and the terminal Z term uses dU/dS only (:654).  The
+    variant, :546-558), or with option_type="put" the put on mean S in the
+    same two variants (no reference counterpart), and the terminal Z term uses dU/dS only (:654).  The
     network takes (t, S, v) -- 1 + 2k inputs -- and is initialised as the
     reference re-initialises it (xavier gain 0.5, zero biases, :580-585).
     An iteration whose loss is NaN is skipped (:409-411).  k > 1 has no
@@ -168,11 +193,15 @@ class HestonFBSNN(FBSNN):
 
     skip_nonfinite = True
     log_print = False             # its progress print is commented out (heston_dnnpde.py:432-434)
+    option_type = "call"          # "put": the put on mean S (set by the constructor)
 
     def __init__(self, Xi, T, M, N, D, Mm, layers, mode, activation, correlation_type="no_correlation",
-                 kappa=2.0, theta=0.2, sigma=0.3, rho=0.8, v0=0.2, payoff_type='discontinuous', device=None):
+                 kappa=2.0, theta=0.2, sigma=0.3, rho=0.8, v0=0.2, payoff_type='discontinuous', device=None, option_type="call"):
         if payoff_type not in ("discontinuous", "continuous"):
             raise ValueError("Invalid payoff type. Choose 'discontinuous' or 'continuous'.")
+        if option_type not in ("call", "put"):
+            raise ValueError("Invalid option type. Choose 'call' or 'put'.")
+        self.option_type = option_type
         self.kappa, self.theta, self.sigma, self.rho, self.v0 = kappa, theta, sigma, rho, v0
         self.payoff_type = payoff_type
         self.n_assets = D
@@ -208,13 +237,19 @@ class HestonFBSNN(FBSNN):
 
     def problem_spec(self):
         smooth = self.payoff_type == "continuous"
-        return ProblemSpec(kind="heston", mu_a=0.05, phi_r=0.05, phi_c=0.0, g="smooth_call" if smooth else "call_mean",
+        if self.option_type == "put":
+            g = "smooth_put" if smooth else "put_mean"
+        else:
+            g = "smooth_call" if smooth else "call_mean"
+        return ProblemSpec(kind="heston", mu_a=0.05, phi_r=0.05, phi_c=0.0, g=g,
                            strike=self.strike, g_alpha=10.0, g_cols=self.n_assets, u_clamp=True, q3=False,
                            kappa=self.kappa, theta=self.theta, sigma=self.sigma, rho=self.rho)
 
     def g_tf(self, X):
         S = X[:, :self.n_assets] if X.dim() > 1 else X
         a = torch.mean(S, dim=1, keepdim=True) - self.strike if S.dim() > 1 else S - self.strike
+        if self.option_type == "put":
+            a = -a
         if self.payoff_type == "discontinuous":
             return torch.maximum(a, torch.tensor(0.0, device=X.device))
         return a / (1 + torch.exp(-10.0 * a))
@@ -322,8 +357,9 @@ class HestonTwoFactorFBSNN(HestonFBSNN):
     independent (fetch_minibatch draws 2k columns).  Limits: no correlation
     between assets (any correlation_type but "no_correlation" raises
     ValueError), no pathwise Monte-Carlo delta (mc_greeks bumps and reprices),
-    and closed_form -- the characteristic-function price -- for one asset and
-    the call payoff only."""
+    and closed_form -- the characteristic-function price of the call or, with
+    option_type="put", the put -- for one asset and the 'discontinuous' payoff
+    only."""
 
     def __init__(self, Xi, T, M, N, D, Mm, layers, mode, activation, correlation_type="no_correlation", **kw):
         if correlation_type != "no_correlation":
@@ -356,9 +392,10 @@ class HestonTwoFactorFBSNN(HestonFBSNN):
         """The Heston characteristic-function price of this object's problem at
         the points (S [R], v [R], t [R]): (price [R, 1], delta [R, 1] = dprice/dS)
         as float32 tensors on the device, through exact("heston", ...)
-        (DBSDE_EXACT_HESTON) with r = 0.05 and this object's strike, kappa,
-        theta, sigma and rho.  One asset and the call payoff ('discontinuous')
-        only: anything else raises ValueError."""
+        (DBSDE_EXACT_HESTON) -- exact("heston_put", ...) for option_type "put"
+        -- with r = 0.05 and this object's strike, kappa, theta, sigma and rho.
+        One asset and the unsmoothed payoff ('discontinuous') only: anything
+        else raises ValueError."""
         if self.n_assets != 1:
             raise ValueError("closed_form exists for one asset only (k = 1)")
         if self.payoff_type != "discontinuous":
@@ -368,9 +405,10 @@ class HestonTwoFactorFBSNN(HestonFBSNN):
         t = torch.as_tensor(np.asarray(t), dtype=torch.float32).to(self.device).reshape(-1)
         if not (S.numel() == v.numel() == t.numel()):
             raise ValueError("S, v and t must hold the same number of points")
-        return _exact("heston", t, torch.stack([S, v], dim=1).contiguous(), self.T,
+        kind = "heston_put" if self.option_type == "put" else "heston"
+        return _exact(kind, t, torch.stack([S, v], dim=1).contiguous(), self.T,
                       (0.05, self.strike, self.kappa, self.theta, self.sigma, self.rho))
 
 
-__all__ = ["CallOption", "CallOption1D", "BasketCallOption", "BSPDETestCase", "HamiltonJacobiBellman",
+__all__ = ["CallOption", "PutOption", "CallOption1D", "BasketCallOption", "BasketPutOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN", "HestonTwoFactorFBSNN"]

@@ -408,7 +408,10 @@ def exact(kind, t, X, T, params):
     kind in {"bsb", "bs_call", "basket_avg", "basket_mean", "heston"}; t [R],
     X [R, D] float32 cuda tensors.  Returns (price, delta); delta is None for
     "bsb".  "heston": the European call of the two-factor Heston model, X [R, 2]
-    = (S, v), params = (r, K, kappa, theta, sigma, rho), delta [R, 1] = dprice/dS."""
+    = (S, v), params = (r, K, kappa, theta, sigma, rho), delta [R, 1] = dprice/dS.
+    "bs_put", "basket_avg_put", "basket_mean_put" and "heston_put" are the
+    European puts with the parameters and shapes of their call counterparts,
+    computed directly (not as the call minus parity)."""
     lib = _lib.load()
     if kind not in _lib.EXACT_KINDS:
         raise ValueError(f"unknown exact solution {kind!r}")
@@ -417,15 +420,16 @@ def exact(kind, t, X, T, params):
     R, D = X.shape
     if t.numel() != R or X.device.type != "cuda" or t.device != X.device:
         raise ValueError("t [R] and X [R, D] must be float32 tensors on the same HIP device")
-    ncol = D if kind == "bs_call" else 1
+    heston = kind in ("heston", "heston_put")
+    ncol = D if kind in ("bs_call", "bs_put") else 1
     price = torch.empty((R, ncol), device=X.device)
     delta = None if kind == "bsb" else torch.empty((R, ncol), device=X.device)
     import numpy as np
     p = np.zeros(6, dtype=np.float64)
-    if len(params) > (6 if kind == "heston" else 3):
+    if len(params) > (6 if heston else 3):
         raise ValueError(f"too many parameters for {kind!r}")
-    if kind == "heston" and len(params) != 6:
-        raise ValueError("'heston' takes params = (r, K, kappa, theta, sigma, rho)")
+    if heston and len(params) != 6:
+        raise ValueError(f"{kind!r} takes params = (r, K, kappa, theta, sigma, rho)")
     p[:len(params)] = params
     s = torch.cuda.current_stream(X.device).cuda_stream
     _lib.check(lib.dbsde_exact(_lib.EXACT_KINDS[kind], _ptr(t), _ptr(X), R, D, float(T),

@@ -61,6 +61,11 @@ extern "C" {
 #define DBSDE_G_LOG 3         /* log(1/2 + 1/2 sum X^2)  hjb_implement.py:597-598     */
 #define DBSDE_G_SMOOTH_CALL 4 /* a / (1 + exp(-alpha a)), a = mean X - K
                                                          heston_dnnpde.py:551-556     */
+/* the puts: the calls in -(. - K); dg/dX_col is -1 (-1/G) in the money, half of
+   that at a tie (torch.maximum's split), 0 out of the money */
+#define DBSDE_G_PUT_SUM 5     /* max(K - sum X, 0)                                    */
+#define DBSDE_G_PUT_MEAN 6    /* max(K - mean X, 0)                                   */
+#define DBSDE_G_SMOOTH_PUT 7  /* a / (1 + exp(-alpha a)), a = K - mean X              */
 
 /* problem kinds */
 #define DBSDE_PROB_DIAG 0     /* mu = mu_a X, sigma = diag(sig_a X + sig_b)          */
@@ -100,12 +105,13 @@ extern "C" {
  *     + rho sigma v S u_Sv + 1/2 sigma^2 v u_vv - phi_r u = 0 per asset.
  *     dbsde_set_corr on such a context is DBSDE_EINVAL (no correlation between
  *     assets), dbsde_mc_value takes neither L nor delta for it, and
- *     DBSDE_EXACT_HESTON is its closed form for k = 1 and a call payoff.
+ *     DBSDE_EXACT_HESTON / DBSDE_EXACT_HESTON_PUT are its closed forms for k = 1
+ *     and a call / put payoff.
  *   kind HESTON_CORR: HESTON's fields, state and step, for dbsde_mc_value alone (the
  *     factor is that call's L argument); dbsde_create refuses it.
  *   phi      =phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
  *   g        = g_kind over the first g_cols state columns (0 = all), strike,
- *              g_alpha (DBSDE_G_SMOOTH_CALL); the terminal |Z - grad g|^2 term
+ *              g_alpha (DBSDE_G_SMOOTH_CALL / _PUT); the terminal |Z - grad g|^2 term
  *              runs over the same columns (heston_dnnpde.py:654: dU/dS only)
  *   u_clamp  = 1: u = max(net(t, X), 0) (heston_dnnpde.py:568)
  *   q3       = 1: for D == 1 reproduce the reference's squeeze() broadcast in
@@ -450,15 +456,31 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
  *                            = 2, theta = 0.2, sigma = 0.3, rho in {0.8, -0.7}
  *                            (DESIGN 5); outside that domain the rule is unchecked.
  *                            Needs sigma > 0, K > 0, S > 0, v >= 0.
+ *   DBSDE_EXACT_BS_PUT, _BASKET_AVG_PUT, _BASKET_MEAN_PUT, _HESTON_PUT
+ *                            the European puts, with the parameters, shapes and ncol
+ *                            of the call counterparts.  Computed directly, not as the
+ *                            call minus parity: K exp(-r tau) N(-d2) - S N(-d1), delta
+ *                            -N(-d1) (a deep out-of-the-money put keeps its relative
+ *                            accuracy); Heston: K exp(-r tau) (1 - P2) - S (1 - P1),
+ *                            delta -(1 - P1), with 1 - P_j = 1/2 - I_j / pi from the
+ *                            call's quadrature sums I_j (same panels, same U).
  * t [R], x [R, D] device fp32; price and delta (nullable) [R * ncol],
- * ncol = D for BS_CALL, 1 otherwise.  At t >= T the payoff and its 0 / 1/2 / 1
- * delta are returned, as the references do.  Computed in fp64.
+ * ncol = D for BS_CALL / BS_PUT, 1 otherwise.  At t >= T the payoff and its
+ * 0 / 1/2 / 1 (put: 0 / -1/2 / -1) delta are returned, as the references do.
+ * Computed in fp64.  DBSDE_EINVAL before any HIP call: an unknown kind; NULL t /
+ * x / params / price; R or D < 1; a Heston kind with D != 2; t, x, price or
+ * delta not aligned to sizeof(float), params not to sizeof(double) (such an
+ * address cannot be the buffer the kernels read and write).
  */
 #define DBSDE_EXACT_BSB 0
 #define DBSDE_EXACT_BS_CALL 1
 #define DBSDE_EXACT_BASKET_AVG 2
 #define DBSDE_EXACT_BASKET_MEAN 3
 #define DBSDE_EXACT_HESTON 4
+#define DBSDE_EXACT_BS_PUT 5
+#define DBSDE_EXACT_BASKET_AVG_PUT 6
+#define DBSDE_EXACT_BASKET_MEAN_PUT 7
+#define DBSDE_EXACT_HESTON_PUT 8
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* hip_stream);
 
@@ -508,7 +530,7 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  *   delta   device [P, D], nullable, DIAG only: the pathwise estimator
  *           exp(-phi_r tau_p) mean_k dg/dX_d(X_T) J_d, J the tangent of the Euler
  *           step, J <- (J + (mu_eff J) dt) + (sig_a J) dW_d, J_0 = 1; 1/2 at the
- *           kink of the call payoffs, 0 in the columns past g_cols.  Heston with
+ *           kink of the call payoffs (-1/2: puts), 0 in the columns past g_cols.  Heston with
  *           delta != NULL is DBSDE_EINVAL (its S and v tangents couple): bump
  *           and reprice on the same draws instead.
  *
