@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("DBSDE_LIB") or os.path.join(LIB_DIR, "libdbsde.so")  
 DBSDE_OK, DBSDE_EINVAL, DBSDE_EHIP, DBSDE_ENOMEM = 0, -1, -2, -3
 
 MODES = {"FC": 0, "NAIS-Net": 1, "Resnet": 2, "Naisnet": 3}
-ACTIVATIONS = {"Sine": 0, "ReLU": 1, "Tanh": 2}
+ACTIVATIONS = {"Sine": 0, "ReLU": 1, "Tanh": 2, "SiLU": 3, "Softplus": 4}
 G_KINDS = {"sumsq": 0, "call_sum": 1, "call_mean": 2, "log": 3, "smooth_call": 4,
            "put_sum": 5, "put_mean": 6, "smooth_put": 7}
 PROBLEM_KINDS = {"diag": 0, "heston": 1, "heston2": 2}

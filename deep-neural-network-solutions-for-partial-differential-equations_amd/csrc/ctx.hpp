@@ -119,7 +119,7 @@ struct dbsde_ctx {
   // C1 is three workgroup lifetimes against A, C's two); DBSDE_CHUNKS=n forces n
   int chunks = 0;
   int cus = 256;   // compute units of the device
-  int fv_slots[64] = {0};   // resident workgroups of the chip per phase variant (lazily queried)
+  int fv_slots[96] = {0};   // resident workgroups of the chip per phase variant (lazily queried)
   int fv_cs = -1;           // the column-split variant of fv (phasecs.hpp), or -1
   int cs_mode = 2;          // 0 off, 1 always, 2 by batch size
 

@@ -65,8 +65,24 @@ struct Mat {
   floatx4 v[TT];
 };
 
+// SiLU / Softplus are straight-line code, and left alone the compiler moves it
+// to where it costs registers.  Phase A: it sinks the derivative's half
+// (reciprocal, select, multiplies) from the forward to its use in the
+// backward, so that s1 holds e and 1 + e per element instead of act'(a), twice
+// the registers (the width-112 phase A spilled 136..255 of them).  Phase C's
+// tangent: SiLU's act'(a) = s + a q spilled 16 registers at width 112 however
+// the prefetch was set.  The empty statement makes its operand a value that
+// exists at that point: act'(a) where phase A stores it, a where SiLU's act_1
+// starts.  For the other activations it is nothing, and they compile to the
+// code they compiled to without it.
+template <int ACT>
+__device__ __forceinline__ void act_pin(float& v) {
+  if constexpr (ACT == ACT_SILU || ACT == ACT_SOFTPLUS) asm volatile("" : "+v"(v));
+}
+
 // activation with compile-time kind: value + first derivative, and first +
-// second derivative (one sincos / tanh per element)
+// second derivative (one sincos / tanh / exponential per element; SiLU and
+// Softplus: act.hpp)
 template <int ACT>
 __device__ __forceinline__ void act_v1(float a, float& f, float& d1) {
   if constexpr (ACT == ACT_SINE) {
@@ -74,7 +90,12 @@ __device__ __forceinline__ void act_v1(float a, float& f, float& d1) {
   } else if constexpr (ACT == ACT_TANH) {
     f = tanhf(a);
     d1 = 1.f - f * f;
+  } else if constexpr (ACT == ACT_SILU) {
+    silu_v1(a, f, d1);
+  } else if constexpr (ACT == ACT_SOFTPLUS) {
+    softplus_v1(a, f, d1);
   } else {
+    static_assert(ACT == ACT_RELU, "unknown activation");
     f = a > 0.f ? a : 0.f;
     d1 = a > 0.f ? 1.f : 0.f;
   }
@@ -88,7 +109,13 @@ __device__ __forceinline__ float act_1(float a) {
   } else if constexpr (ACT == ACT_TANH) {
     const float f = tanhf(a);
     return 1.f - f * f;
+  } else if constexpr (ACT == ACT_SILU) {
+    act_pin<ACT>(a);
+    return silu_1(a);
+  } else if constexpr (ACT == ACT_SOFTPLUS) {
+    return softplus_1(a);
   } else {
+    static_assert(ACT == ACT_RELU, "unknown activation");
     return a > 0.f ? 1.f : 0.f;
   }
 }
@@ -102,7 +129,12 @@ __device__ __forceinline__ void act_12(float a, float& d1, float& d2) {
     const float f = tanhf(a);
     d1 = 1.f - f * f;
     d2 = -2.f * f * d1;
+  } else if constexpr (ACT == ACT_SILU) {
+    silu_12(a, d1, d2);
+  } else if constexpr (ACT == ACT_SOFTPLUS) {
+    softplus_12(a, d1, d2);   // no logarithm: phase C needs the derivatives only
   } else {
+    static_assert(ACT == ACT_RELU, "unknown activation");
     d1 = a > 0.f ? 1.f : 0.f;
     d2 = 0.f;
   }

@@ -3,7 +3,12 @@
 // Row layout: one "row" = one (path m, time n) pair, r = m*(N+1)+n, exactly the
 // reference's X[M, N+1, D] order (DeepBSDE.py:242).  All activation buffers are
 // row-major [Rp, ld] fp32 with Rp a multiple of 64 and ld a multiple of 16.
-// Padding rows/columns are zero and stay zero (every activation has act(0)=0).
+// Padding rows/columns of the pre-activations are zero and stay zero.  With
+// act(0) = 0 (Sine, ReLU, Tanh, SiLU) so are the hidden states; Softplus leaves
+// log 2 there, which nothing reads into a result: a padding column meets zero
+// weight columns in the next layer and in w_out, and only the padded part of
+// a weight-gradient tile, which no finalize window covers; a padding row
+// carries no cotangent (row_cotan), so it adds nothing to any gradient.
 //
 // Unified network (see oracle/timeparallel.py for the derivation):
 //   a_0 = x W_in^T + b_in,  h_1 = act(a_0)
@@ -14,11 +19,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "act.hpp"
+
 namespace dbsde {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-enum Act { ACT_SINE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+enum Act { ACT_SINE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_SILU = 3, ACT_SOFTPLUS = 4 };
 
 // sin and cos together on the transcendental unit: a is reduced modulo 2*pi in
 // radians (two-part Cody-Waite 2*pi in fp32, |r| <= pi), scaled to revolutions
@@ -44,6 +51,8 @@ __device__ __forceinline__ float act_f(int act, float a) {
     return sv;
   }
   if (act == ACT_TANH) return tanhf(a);
+  if (act == ACT_SILU) return silu_f(a);
+  if (act == ACT_SOFTPLUS) return softplus_f(a);
   return a > 0.f ? a : 0.f;
 }
 __device__ __forceinline__ float act_d1(int act, float a) {
@@ -56,6 +65,8 @@ __device__ __forceinline__ float act_d1(int act, float a) {
     float t = tanhf(a);
     return 1.f - t * t;
   }
+  if (act == ACT_SILU) return silu_1(a);
+  if (act == ACT_SOFTPLUS) return softplus_1(a);
   return a > 0.f ? 1.f : 0.f;
 }
 __device__ __forceinline__ void act_d12(int act, float a, float& d1, float& d2) {
@@ -68,6 +79,10 @@ __device__ __forceinline__ void act_d12(int act, float a, float& d1, float& d2) 
     float t = tanhf(a);
     d1 = 1.f - t * t;
     d2 = -2.f * t * d1;
+  } else if (act == ACT_SILU) {
+    silu_12(a, d1, d2);
+  } else if (act == ACT_SOFTPLUS) {
+    softplus_12(a, d1, d2);
   } else {
     d1 = a > 0.f ? 1.f : 0.f;
     d2 = 0.f;

@@ -173,7 +173,7 @@ int build_net(dbsde_ctx* c) {
   c->K = n - 3;   // 1..6 hidden blocks
   c->mode = g.mode;
   c->act = g.activation;
-  if (c->act < 0 || c->act > 2) return fail(c, DBSDE_EINVAL, "unknown activation");
+  if (c->act < DBSDE_ACT_SINE || c->act > DBSDE_ACT_SOFTPLUS) return fail(c, DBSDE_EINVAL, "unknown activation");
   long long off = 0;
   auto lin = [&](int o, int i) {
     Lin l;

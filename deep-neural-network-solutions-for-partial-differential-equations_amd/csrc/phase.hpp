@@ -626,6 +626,7 @@ __global__ void __launch_bounds__(64 * P3_WAVES, 2 * P3_WAVES / 4) phaseA_kernel
     for (int r = 0; r < 4; ++r) {
       float f, d;
       act_v1<ACT>(acc.v[o][r], f, d);
+      act_pin<ACT>(d);
       h.v[o][r] = f;
       if constexpr (!RECOMP) s1[0].v[o][r] = d;
     }
@@ -649,6 +650,7 @@ __global__ void __launch_bounds__(64 * P3_WAVES, 2 * P3_WAVES / 4) phaseA_kernel
       for (int r = 0; r < 4; ++r) {
         float f, d;
         act_v1<ACT>(acc.v[o][r], f, d);
+        act_pin<ACT>(d);
         if constexpr (!RECOMP) s1[j].v[o][r] = d;
         h.v[o][r] = f + p.rho * h.v[o][r];
       }

@@ -45,7 +45,9 @@ __global__ void __launch_bounds__(64 * P3_WAVES, 1) phaseC2_kernel(FusedArgs p);
 // phase section at the north star)
 #define DBSDE_PHASE2_INSTANCES(X)                                                                   \
   X(16, 7, 3, 0, false, 1, 3, true) X(16, 7, 3, 1, false, 1, 3, true) X(16, 7, 3, 2, false, 1, 3, true) \
-  X(16, 1, 3, 0, false, 1, 3, true) X(16, 1, 3, 1, false, 1, 3, true) X(16, 1, 3, 2, false, 1, 3, true)
+  X(16, 1, 3, 0, false, 1, 3, true) X(16, 1, 3, 1, false, 1, 3, true) X(16, 1, 3, 2, false, 1, 3, true) \
+  X(16, 7, 3, 3, false, 1, 3, true) X(16, 7, 3, 4, false, 1, 3, true) X(16, 1, 3, 3, false, 1, 3, true) \
+  X(16, 1, 3, 4, false, 1, 3, true)
 #define DBSDE_PHASE2_EXTERN(T, TD, K, ACT, HV, NT, NBUF, ADOT)                                   \
   extern template __global__ void phaseA2_kernel<T, TD, K, ACT, HV, NT, NBUF, ADOT>(FusedArgs); \
   extern template __global__ void phaseC2_kernel<T, TD, K, ACT, HV, NT, NBUF, ADOT>(FusedArgs);

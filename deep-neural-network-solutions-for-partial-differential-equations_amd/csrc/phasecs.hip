@@ -343,6 +343,7 @@ __global__ void __launch_bounds__(64 * P3_WAVES, 2) phaseAcs_kernel(FusedArgs p)
     for (int r = 0; r < 4; ++r) {
       float f, d;
       act_v1<ACT>(acc.v[o][r], f, d);
+      act_pin<ACT>(d);
       ho.v[o][r] = f;
       s1[0].v[o][r] = d;
     }
@@ -369,6 +370,7 @@ __global__ void __launch_bounds__(64 * P3_WAVES, 2) phaseAcs_kernel(FusedArgs p)
       for (int r = 0; r < 4; ++r) {
         float f, d;
         act_v1<ACT>(acc.v[o][r], f, d);
+        act_pin<ACT>(d);
         s1[j].v[o][r] = d;
         ho.v[o][r] = f + p.rho * ho.v[o][r];
       }

@@ -33,9 +33,10 @@ template <int T, int TD, int K, int ACT, bool HV>
 __global__ void __launch_bounds__(64 * P3_WAVES, 2) phaseCcs_kernel(FusedArgs p);
 
 // the instantiations phasecs.hip builds: the width-112 split-bf16 networks
-// (NAIS-Net / Naisnet with the x-stack, FC / Resnet without) x 3 activations
+// (NAIS-Net / Naisnet with the x-stack, FC / Resnet without) x 5 activations
 #define DBSDE_PHASECS_INSTANCES(X) \
-  X(7, 7, 3, 0, true) X(7, 7, 3, 1, true) X(7, 7, 3, 2, true) X(7, 7, 3, 0, false) X(7, 7, 3, 1, false) X(7, 7, 3, 2, false)
+  X(7, 7, 3, 0, true) X(7, 7, 3, 1, true) X(7, 7, 3, 2, true) X(7, 7, 3, 0, false) X(7, 7, 3, 1, false) X(7, 7, 3, 2, false) \
+  X(7, 7, 3, 3, true) X(7, 7, 3, 4, true) X(7, 7, 3, 3, false) X(7, 7, 3, 4, false)
 #define DBSDE_PHASECS_EXTERN(T, TD, K, ACT, HV)                                   \
   extern template __global__ void phaseAcs_kernel<T, TD, K, ACT, HV>(FusedArgs); \
   extern template __global__ void phaseCcs_kernel<T, TD, K, ACT, HV>(FusedArgs);

@@ -58,13 +58,16 @@ const FusedVariant kFused[] = {
     FV2(7, 7, 3, 0, 1), FV2(7, 7, 3, 1, 1), FV2(7, 7, 3, 2, 1), FV2(7, 7, 3, 0, 0), FV2(7, 7, 3, 1, 0),
     FV2(7, 7, 3, 2, 0), FV2(1, 1, 1, 0, 0), FV2(1, 1, 1, 1, 0), FV2(1, 1, 1, 2, 0), FV2(1, 1, 2, 0, 0),
     FV2(1, 1, 2, 1, 0), FV2(1, 1, 2, 2, 0), FV2(1, 1, 3, 0, 0), FV2(1, 1, 3, 1, 0), FV2(1, 1, 3, 2, 0),
+    // SiLU (3) and Softplus (4): the instances tanh has
+    FV2(7, 7, 3, 3, 1), FV2(7, 7, 3, 4, 1), FV2(7, 7, 3, 3, 0), FV2(7, 7, 3, 4, 0), FV2(1, 1, 1, 3, 0),
+    FV2(1, 1, 1, 4, 0), FV2(1, 1, 2, 3, 0), FV2(1, 1, 2, 4, 0), FV2(1, 1, 3, 3, 0), FV2(1, 1, 3, 4, 0),
 };
 #undef FQ
 #undef FCS
 #undef FV2
 #undef FV
 constexpr int kNumFused = (int)(sizeof(kFused) / sizeof(kFused[0]));
-static_assert(kNumFused <= 64, "dbsde_ctx::fv_slots");
+static_assert(kNumFused <= 96, "dbsde_ctx::fv_slots");
 const FusedVariant& fused_at(int fv) { return kFused[fv]; }
 // the variant for a network (each (T, TD, K, act, hv, x3) has at most one
 // 64-row and one column-split instance)

@@ -29,7 +29,7 @@ class Sine(nn.Module):
 
 
 def activation_module(name):
-    table = {"Sine": Sine, "ReLU": nn.ReLU, "Tanh": nn.Tanh}
+    table = {"Sine": Sine, "ReLU": nn.ReLU, "Tanh": nn.Tanh, "SiLU": nn.SiLU, "Softplus": nn.Softplus}
     if name not in table:
         raise ValueError(f"activation {name!r} is not one of {sorted(table)}")
     return table[name]()

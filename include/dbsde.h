@@ -48,10 +48,16 @@ extern "C" {
 #define DBSDE_MODE_RESNET 2    /* "Resnet"   Resnet(stable=False)                   */
 #define DBSDE_MODE_NAISNET 3   /* "Naisnet"  Functions/naisnet.py:6-96              */
 
-/* activations: Functions/Sine.py, nn.ReLU, nn.Tanh */
+/* activations: Functions/Sine.py, nn.ReLU, nn.Tanh (the reference's three);
+   nn.SiLU and nn.Softplus (beta = 1, the smooth form at every argument: torch's
+   switch to the identity above 20 changes less than fp32 resolves there) are
+   the smooth non-saturating ones this library adds.  Any other value is
+   DBSDE_EINVAL. */
 #define DBSDE_ACT_SINE 0
 #define DBSDE_ACT_RELU 1
 #define DBSDE_ACT_TANH 2
+#define DBSDE_ACT_SILU 3
+#define DBSDE_ACT_SOFTPLUS 4
 
 /* terminal conditions g(X) over the leading g_cols state columns */
 #define DBSDE_G_SUMSQ 0       /* sum X^2                 DeepBSDE.py:333-335          */
