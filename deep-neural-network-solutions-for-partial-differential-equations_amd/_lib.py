@@ -20,6 +20,7 @@ G_KINDS = {"sumsq": 0, "call_sum": 1, "call_mean": 2, "log": 3, "smooth_call": 4
            "put_sum": 5, "put_mean": 6, "smooth_put": 7}
 PROBLEM_KINDS = {"diag": 0, "heston": 1, "heston2": 2}
 PROB_HESTON_CORR = 3   # dbsde_mc_value's kind for "heston" with a factor between the assets: not a context kind
+PROB_ASIAN = 4         # ProblemSpec(kind="diag", average=True): state [A, S_1..S_k], A the running average
 OPTIMIZERS = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3, "Adagrad": 4, "Adamax": 5, "Adadelta": 6, "ASGD": 7}
 EXACT_KINDS = {"bsb": 0, "bs_call": 1, "basket_avg": 2, "basket_mean": 3, "heston": 4,
                "bs_put": 5, "basket_avg_put": 6, "basket_mean_put": 7, "heston_put": 8}

@@ -36,6 +36,17 @@ constexpr int DP_MAX = 1024;
 // spare zero rows of BtZ behind Dp for the wide Z GEMM's ragged last column tile
 constexpr int ZG_PAD = 128;
 
+// DBSDE_PROB_ASIAN (state [A, S_1..S_k], D = k + 1): why dbsde_create and
+// dbsde_mc_value refuse the problem, or null
+inline const char* asian_refusal(const dbsde_problem& pr, int D) {
+  if (D < 2) return "the Asian state is [A, S_1..S_k]: D must be >= 2";
+  if (pr.phi_c != 0.f) return "the Asian problem needs phi_c == 0 (X.Z would include A u_A)";
+  if (pr.g_cols != 1) return "the Asian payoff is on the running average alone: g_cols must be 1";
+  if (pr.g_kind == DBSDE_G_SUMSQ || pr.g_kind == DBSDE_G_LOG)
+    return "the Asian problem takes the call and put payoffs only (not sumsq or log)";
+  return nullptr;
+}
+
 struct Lin {
   long long w = -1, b = -1;
   int out = 0, in = 0;
@@ -125,7 +136,8 @@ struct dbsde_ctx {
 
   // ---- network description
   int mode = 0, act = 0, K = 0, D = 0;
-  int nb = 0;                 // Brownian dimension (D; D/2 for Heston, kind 1)
+  int nb = 0;                 // Brownian dimension (D; D/2 for Heston, kind 1; D - 1 for Asian, kind 4)
+  bool asian = false;         // DBSDE_PROB_ASIAN: state [A, S_1..S_k], A the running average (nb = D - 1)
   int gcols = 0;              // state columns entering g and the terminal Z loss
   bool heston = false, u_clamp = false;
   bool heston2 = false;       // DBSDE_PROB_HESTON2: two Brownian motions per asset (nb = D)

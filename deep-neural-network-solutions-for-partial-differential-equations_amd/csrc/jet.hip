@@ -336,6 +336,8 @@ struct PdeArgs {
   dbsde_problem pr;
   int heston, D, nb, nd;   // heston: 0 DIAG, 1 HESTON, 2 HESTON2
   float rhob;              // HESTON2: fp32(sqrt(1 - (double)h_rho^2))
+  int asian;               // DBSDE_PROB_ASIAN: state [A, S_1..S_nb] (heston = 0)
+  float T;                 // its averaging horizon
   const float* Lt;      // [nb][nb] L^T (dbsde_set_corr) or null
   const float* X;
   long long r0;          // the chunk's first point
@@ -353,7 +355,9 @@ struct PdeArgs {
 // plane with the rollout's own coefficients (heston_coef, sde.hpp),
 // and with a factor L between the assets column j of Sigma(x) . L: for every
 // asset i >= j the (S_i, v_i) entries of Sigma_i . (1, 1)^T times L[i][j];
-// two-factor Heston (nd = 1 + 2k) the 2k columns of its diffusion matrix
+// two-factor Heston (nd = 1 + 2k) the 2k columns of its diffusion matrix;
+// arithmetic average (state [A, S_1..S_k], nd = 1 + k) DIAG's columns over the
+// S columns with A component 0
 __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
   const int ld = a.D + 1;
   const long long n = (long long)a.np * a.nd * ld;
@@ -386,6 +390,13 @@ __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
         const HestonCoef h = heston_coef(a.pr.mu_a, a.pr.h_kappa, a.pr.h_theta, a.pr.h_sigma, a.pr.h_rho, x[i], x[k + i]);
         v = d < k ? h.d00 + h.d01 : h.d10 + h.d11;
         if (a.Lt) v *= a.Lt[(size_t)jb * k + i];   // L[i][jb]
+      }
+    } else if (a.asian) {
+      // [A, S_1..S_k]: direction 1 + j is column j of diag(sig_a S + sig_b) . L in the S columns, 0 in A
+      const int i = d - 1;
+      if (i >= 0) {
+        const float l = a.Lt ? (jb <= i ? a.Lt[(size_t)jb * a.nb + i] : 0.f) : (i == jb ? 1.f : 0.f);
+        v = (a.pr.sig_a * x[d] + a.pr.sig_b) * l;
       }
     } else {
       const float l = a.Lt ? (jb <= d ? a.Lt[(size_t)jb * a.nb + d] : 0.f) : (d == jb ? 1.f : 0.f);
@@ -422,6 +433,17 @@ __global__ void __launch_bounds__(256) pde_terms_kernel(PdeArgs a) {
     drift += mu * zd;
     xz += xd * zd;
     zz += zd * zd;
+  }
+  if (a.asian) {
+    // [A, S_1..S_k]: mu_a S_i on the S columns and mean S / T on A
+    float ss = 0.f;
+    drift = 0.f;
+    for (int d = 1 + lane; d < D; d += 64) {
+      ss += x[d];
+      drift += a.pr.mu_a * x[d] * du[d];
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) drift += ss / (float)a.nb / a.T * du[0];
   }
   float tr = 0.f, atr = 0.f;
   for (int j = 1 + lane; j < a.nd; j += 64) {
@@ -674,6 +696,8 @@ int dbsde_pde_residual(dbsde_ctx* c, const float* params, int R, const float* t,
     pa.pr = c->cfg.problem;
     pa.heston = c->heston2 ? 2 : (c->heston ? 1 : 0);
     pa.rhob = c->rhob;
+    pa.asian = c->asian ? 1 : 0;
+    pa.T = c->cfg.T;
     pa.D = D;
     pa.nb = c->nb;
     pa.nd = nd;

@@ -17,6 +17,14 @@
 // those of coordinates d (W^S_d) and nd + d (W^v_d), nd = D / 2 -- the
 // increments rollout_heston2_kernel draws.  phi_zz != 0 (HJB) is not linear:
 // dbsde_hjb_mc.
+// Arithmetic average (DBSDE_PROB_ASIAN, path kinds MC_ASIAN / MC_ASIAN_CORR):
+// state [A, S_1..S_k], nd = k; thread (sample, asset d) runs diag_step on S_d
+// and accumulates I_d = sum_n (double)fp32(S_{d,n} dt_n) (the left-point rule
+// of asian_step, sde.hpp) -- no reduction per step.  A sample's payoff terms are
+// its I_d: the end-of-path LDS reduction sums them in order, A_T = A_p +
+// (sum_d I_d) / (k T) (T the averaging horizon, not tau_p), and mc_payoff runs
+// with one column.  Delta: dA_T/dA_p = 1 (the reducing threads sum dg/dA_T),
+// dA_T/dS_d = (sum_n (double)fp32(J_{d,n} dt_n)) / (k T) with DIAG's tangent J.
 //
 // Draws.  The normals of sample k, step n, Brownian coordinate d are
 // philox_normal4(seed, offset, k, n >> 2, d)[n & 3] -- the device-mode rollout's
@@ -93,7 +101,10 @@ constexpr int MC_LPACK = MC_NBMAX * (MC_NBMAX + 1) / 2;
 constexpr int MC_HCMAX = 511;      // correlated Heston: dbsde_set_corr's limit for Heston contexts
 constexpr int MC_WS_MB = 1024;     // correlated Heston: default workspace bound (DBSDE_MC_WS_MB)
 constexpr int MC_ZMAX = 2048;       // correlated: floats of the Z (and C) tile, nd x (4 S padded to 16) <= 2048
-enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2, MC_HESTON2 = 3 };
+enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2, MC_HESTON2 = 3, MC_ASIAN = 4, MC_ASIAN_CORR = 5 };
+// the kinds whose increments go through the L . Z product, and the arithmetic-average kinds
+constexpr bool mc_corr(int kind) { return kind == MC_CORR || kind == MC_ASIAN_CORR; }
+constexpr bool mc_asian(int kind) { return kind == MC_ASIAN || kind == MC_ASIAN_CORR; }
 
 typedef float mcf4 __attribute__((ext_vector_type(4)));
 
@@ -187,7 +198,7 @@ __device__ __forceinline__ void mc_payoff(int g_kind, double s, double cols, dou
 template <int KIND, bool DELTA, bool WS>
 __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int s, bool act, int p0,
                                         const float (&sq)[MC_PT], float (&X)[MC_PT], float (&V)[MC_PT], float* zs,
-                                        const float* Ls, const float* wz) {
+                                        const float* Ls, const float* wz, double (&AI)[MC_PT], double (&AJ)[MC_PT]) {
   for (int n0 = 0; n0 < a.n_steps; n0 += 4) {
     float z[4];
     if constexpr (WS) {
@@ -198,7 +209,7 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
     }
     float zv[4] = {0.f, 0.f, 0.f, 0.f};   // two-factor Heston: the normals of W^v_d, coordinate nd + d
     if constexpr (KIND == MC_HESTON2) philox_normal4(a.seed, a.offset, k, (uint32_t)(n0 >> 2), (uint32_t)(a.nd + d), zv);
-    if constexpr (KIND == MC_CORR) {
+    if constexpr (mc_corr(KIND)) {
       // dW^T = L . Z on the matrix cores.  Z [nd][NCp]: row j = coordinate, column
       // 4 s + i = step i of sample slot s (NCp = the 4 S columns padded to 16).
       // One v_mfma_f32_16x16x4_f32 per (16-row block o of L, 16-column block cb,
@@ -262,13 +273,17 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
           float sa, sb;
           heston_step(heston_coef(a.mu, a.kappa, a.theta, a.hsig, a.rho, X[i], V[i]), dt, w, X[i], V[i], sa, sb);
         } else {
+          if constexpr (mc_asian(KIND)) {   // the left-point rule: S (and J) at the start of the step
+            AI[i] += (double)rn_mul(X[i], dt);
+            if constexpr (DELTA) AJ[i] += (double)rn_mul(V[i], dt);
+          }
           diag_step(a.mu, a.sig_a, a.sig_b, dt, w, X[i]);
           if constexpr (DELTA) diag_tangent_step(a.mu, a.sig_a, dt, w, V[i]);
         }
       }
     }
   }
-  if constexpr (KIND == MC_CORR) __syncthreads();   // the C tile shares LDS with what the caller writes next
+  if constexpr (mc_corr(KIND)) __syncthreads();   // the C tile shares LDS with what the caller writes next
 }
 
 template <int KIND, bool DELTA, bool WS = false>
@@ -280,13 +295,13 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
   // path's last barrier and read before the next path's first)
   static_assert(sizeof(fred) >= 2 * MC_ZMAX * sizeof(float), "Z and C tiles must fit fred");
   float* zs = reinterpret_cast<float*>(fred);
-  __shared__ float Ls[KIND == MC_CORR ? MC_LPACK : 1];
+  __shared__ float Ls[mc_corr(KIND) ? MC_LPACK : 1];
   const int tid = threadIdx.x;
   int ch = blockIdx.y;
   if constexpr (WS) ch += a.ch0;
   const int p0 = blockIdx.x * MC_PT;
   const int nd = a.nd, S = a.S, nj = a.nj;
-  if constexpr (KIND == MC_CORR)
+  if constexpr (mc_corr(KIND))
     for (int e = tid; e < nd * (nd + 1) / 2; e += MC_THREADS) Ls[e] = a.Lp[e];   // read after mc_path's first barrier
   const bool act = nj > 1 || tid < S * nd;
   const int s = (act && nj == 1) ? tid / nd : 0;
@@ -296,6 +311,11 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
   const bool reducer = rs < S;
   const bool squares = mc_squares(a.g_kind);
   const double cols = (double)a.gcols, K = (double)a.strike, alpha = (double)a.g_alpha;
+  // arithmetic average: the state columns are [A, S_1..S_nd], a sample's payoff terms are the
+  // time integrals I_d of its assets, and A_T = A_p + (sum_d I_d) / (nd T)
+  constexpr bool ASIAN = mc_asian(KIND);
+  constexpr int XO = ASIAN ? 1 : 0;
+  const double akt = (double)nd * (double)a.T;
   float sq[MC_PT];
   int pc[MC_PT];
 #pragma unroll
@@ -305,6 +325,7 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
   }
   const long long k0 = (long long)ch * a.per, k1 = k0 + a.per < a.mc ? k0 + a.per : a.mc;
   double gs = 0.0, g2 = 0.0;
+  double gps = 0.0;   // ASIAN with DELTA: sum of dg/dA_T, the A column of delta
   double dacc[MC_PT];
 #pragma unroll
   for (int i = 0; i < MC_PT; ++i) dacc[i] = 0.0;
@@ -314,6 +335,7 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
     const bool live = act && kk < k1;
     float X[MC_PT], V[MC_PT];
     double fs[MC_PT];
+    double AI[MC_PT], AJ[MC_PT];   // ASIAN: sum_n fp32(S_n dt_n) and sum_n fp32(J_n dt_n) of the thread's asset
 #pragma unroll
     for (int i = 0; i < MC_PT; ++i) fs[i] = 0.0;
     for (int j = 0; j < nj; ++j) {
@@ -322,16 +344,21 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
       const int dd = dl ? d : 0;
 #pragma unroll
       for (int i = 0; i < MC_PT; ++i) {
-        X[i] = a.x[(size_t)pc[i] * a.D + dd];
+        X[i] = a.x[(size_t)pc[i] * a.D + XO + dd];
         V[i] = (KIND == MC_HESTON || KIND == MC_HESTON2) ? a.x[(size_t)pc[i] * a.D + nd + dd] : 1.f;
+        AI[i] = AJ[i] = 0.0;
       }
       const float* wz = nullptr;
       if constexpr (WS)
         if (dl) wz = a.ws + (size_t)(kk - a.ws_k0) * a.n_steps * nd + dd;
-      mc_path<KIND, DELTA, WS>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls, wz);
+      mc_path<KIND, DELTA, WS>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls, wz, AI, AJ);
       if (dl) {
 #pragma unroll
         for (int i = 0; i < MC_PT; ++i) {
+          if constexpr (ASIAN) {
+            fs[i] += AI[i];
+            continue;
+          }
           if (dd < a.gcols) fs[i] += squares ? (double)X[i] * (double)X[i] : (double)X[i];
           if ((KIND == MC_HESTON || KIND == MC_HESTON2) && nd + dd < a.gcols)
             fs[i] += squares ? (double)V[i] * (double)V[i] : (double)V[i];
@@ -345,11 +372,13 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
       const double* fr = fred + ri * MC_THREADS + rs * RW;
       double sum = 0.0;
       for (int e = 0; e < RW; ++e) sum += fr[e];
+      if constexpr (ASIAN) sum = (double)a.x[(size_t)(p0 + ri < a.P ? p0 + ri : a.P - 1) * a.D] + sum / akt;   // A_T
       double g, gp;
       mc_payoff(a.g_kind, sum, cols, K, alpha, g, gp);
       if (kb + rs < k1) {
         gs += g;
         g2 += g * g;
+        if constexpr (ASIAN && DELTA) gps += gp;
       }
       gpl[tid] = (float)gp;
     }
@@ -362,20 +391,22 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
         if (nj > 1) {   // the coordinates of a long state are run again now that dg/da is known
 #pragma unroll
           for (int i = 0; i < MC_PT; ++i) {
-            X[i] = a.x[(size_t)pc[i] * a.D + dd];
+            X[i] = a.x[(size_t)pc[i] * a.D + XO + dd];
             V[i] = 1.f;
+            AI[i] = AJ[i] = 0.0;
           }
-          mc_path<KIND, DELTA, WS>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls, nullptr);
+          mc_path<KIND, DELTA, WS>(a, (uint32_t)kk, dd, s, act, p0, sq, X, V, zs, Ls, nullptr, AI, AJ);
         }
         if (!dl) continue;
 #pragma unroll
         for (int i = 0; i < MC_PT; ++i) {
           const double fp = dd < a.gcols ? (squares ? 2.0 * (double)X[i] : 1.0) : 0.0;
-          const double v = (double)gpl[s * MC_PT + i] * fp * (double)V[i];
+          double v = (double)gpl[s * MC_PT + i] * fp * (double)V[i];
+          if constexpr (ASIAN) v = (double)gpl[s * MC_PT + i] * (AJ[i] / akt);   // dA_T / dS_d = (sum_n J_n dt_n) / (nd T)
           if (nj == 1) {
             dacc[i] += v;
           } else if (p0 + i < a.P) {   // the thread's own slot: first sample stores, the others add
-            double* q = a.part + ((size_t)(p0 + i) * a.nch + ch) * a.W + 2 + dd;
+            double* q = a.part + ((size_t)(p0 + i) * a.nch + ch) * a.W + 2 + XO + dd;
             *q = kb == k0 ? v : *q + v;
           }
         }
@@ -387,17 +418,20 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
   if (reducer) {
     fred[tid] = gs;
     fred[MC_THREADS + tid] = g2;
+    if constexpr (ASIAN && DELTA) fred[2 * MC_THREADS + tid] = gps;
   }
   __syncthreads();
   if (tid < MC_PT && p0 + tid < a.P) {
-    double s1 = 0.0, s2 = 0.0;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int r = 0; r < S; ++r) {
       s1 += fred[r * MC_PT + tid];
       s2 += fred[MC_THREADS + r * MC_PT + tid];
+      if constexpr (ASIAN && DELTA) s3 += fred[2 * MC_THREADS + r * MC_PT + tid];
     }
     double* q = a.part + ((size_t)(p0 + tid) * a.nch + ch) * a.W;
     q[0] = s1;
     q[1] = s2;
+    if constexpr (ASIAN && DELTA) q[2] = s3;   // dA_T / dA_p = 1
   }
   if constexpr (DELTA) {
     if (nj == 1) {
@@ -410,7 +444,7 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
         if (p0 + i >= a.P) continue;
         double sum = 0.0;
         for (int r = 0; r < S; ++r) sum += fred[i * MC_THREADS + r * nd + d];
-        a.part[((size_t)(p0 + i) * a.nch + ch) * a.W + 2 + d] = sum;
+        a.part[((size_t)(p0 + i) * a.nch + ch) * a.W + 2 + XO + d] = sum;
       }
     }
   }
@@ -475,7 +509,7 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (mc > (1LL << 32)) return bad("mc must be <= 2^32 (the sample index is a 32-bit counter word)");
   if (D > MC_DMAX) return bad("D must be <= 4096");
   if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2 &&
-      prob->kind != DBSDE_PROB_HESTON_CORR)
+      prob->kind != DBSDE_PROB_HESTON_CORR && prob->kind != DBSDE_PROB_ASIAN)
     return bad("unknown problem kind");
   if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_PUT) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
@@ -491,11 +525,17 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
     return bad("no pathwise delta for Heston (the S and v tangents couple); bump and reprice on the same draws");
   if (hcorr && D / 2 > MC_HCMAX) return bad("correlated Heston needs k = D / 2 <= 511");
   if (hcorr && (n_steps + 3) / 4 > 65535) return bad("correlated Heston needs n_steps <= 262140");
-  if (!hcorr && L && D > MC_NBMAX) return bad("L needs D <= 128");
+  // arithmetic average: state [A, S_1..S_k], the DIAG process on the k = D - 1 assets, payoff on A
+  const bool asian = prob->kind == DBSDE_PROB_ASIAN;
+  if (asian) {
+    if (const char* why = asian_refusal(*prob, D)) return bad(why);
+    if (L && D - 1 > MC_NBMAX) return bad("L needs D - 1 <= 128 assets");
+  }
+  if (!hcorr && !asian && L && D > MC_NBMAX) return bad("L needs D <= 128");
 
   McArgs a{};
   a.D = D;
-  a.nd = heston ? D / 2 : D;
+  a.nd = heston ? D / 2 : (asian ? D - 1 : D);
   a.P = P;
   const int tiles = (P + MC_PT - 1) / MC_PT;
   a.Ppad = tiles * MC_PT;
@@ -507,7 +547,7 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   a.nch = (int)((mc + a.per - 1) / a.per);
   a.W = 2 + (delta ? D : 0);
   a.g_kind = prob->g_kind;
-  a.gcols = prob->g_cols > 0 && prob->g_cols < D ? prob->g_cols : D;
+  a.gcols = prob->g_cols > 0 && prob->g_cols < D ? prob->g_cols : D;   // (ASIAN: 1, the A column)
   a.strike = prob->strike;
   a.g_alpha = prob->g_alpha;
   a.phi_r = prob->phi_r;
@@ -581,6 +621,14 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
     mc_kernel<MC_HESTON2, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (heston)
     mc_kernel<MC_HESTON, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (asian && L && delta)
+    mc_kernel<MC_ASIAN_CORR, true><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (asian && L)
+    mc_kernel<MC_ASIAN_CORR, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (asian && delta)
+    mc_kernel<MC_ASIAN, true><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (asian)
+    mc_kernel<MC_ASIAN, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (L && delta)
     mc_kernel<MC_CORR, true><<<grid, MC_THREADS, 0, st>>>(a);
   else if (L)

@@ -281,18 +281,23 @@ int build_net(dbsde_ctx* c) {
     return fail(c, DBSDE_EINVAL,
                 "DBSDE_PROB_HESTON_CORR is dbsde_mc_value's kind: a context takes kind DBSDE_PROB_HESTON plus "
                 "dbsde_set_corr");
-  if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON && pr.kind != DBSDE_PROB_HESTON2)
+  if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON && pr.kind != DBSDE_PROB_HESTON2 &&
+      pr.kind != DBSDE_PROB_ASIAN)
     return fail(c, DBSDE_EINVAL, "unknown problem kind");
   if (pr.g_kind < 0 || pr.g_kind > DBSDE_G_SMOOTH_PUT) return fail(c, DBSDE_EINVAL, "unknown terminal condition");
   c->heston = pr.kind == DBSDE_PROB_HESTON;
   c->heston2 = pr.kind == DBSDE_PROB_HESTON2;
+  c->asian = pr.kind == DBSDE_PROB_ASIAN;
+  if (c->asian) {
+    if (const char* why = asian_refusal(pr, c->D)) return fail(c, DBSDE_EINVAL, why);
+  }
   if ((c->heston || c->heston2) && c->D % 2 != 0)
     return fail(c, DBSDE_EINVAL, "Heston state is [S_1..S_k, v_1..v_k]: layers[0] - 1 must be even");
   // two-factor Heston: |rho| <= 1, and the v-column weight of the second Brownian motion
   if (c->heston2 && !(std::fabs((double)pr.h_rho) <= 1.0))
     return fail(c, DBSDE_EINVAL, "two-factor Heston needs |h_rho| <= 1");
   c->rhob = c->heston2 ? (float)std::sqrt(1.0 - (double)pr.h_rho * (double)pr.h_rho) : 0.f;
-  c->nb = c->heston ? c->D / 2 : c->D;
+  c->nb = c->heston ? c->D / 2 : (c->asian ? c->D - 1 : c->D);
   c->gcols = pr.g_cols > 0 ? pr.g_cols : c->D;
   if (c->gcols > c->D) return fail(c, DBSDE_EINVAL, "g_cols exceeds the state dimension");
   c->u_clamp = pr.u_clamp != 0;
@@ -732,6 +737,10 @@ int dbsde_create(const dbsde_config* cfg, dbsde_ctx** out) {
     dbsde_destroy(c);
     return rc;
   }
+  // (dbsde_last_error(NULL) is the message of the last FAILED call without a
+  // context: a context that exists has none, so an earlier refusal's text must
+  // not read as this call's)
+  g_last_error.clear();
   *out = c;
   return DBSDE_OK;
 }

@@ -878,6 +878,182 @@ __global__ void __launch_bounds__(H2_THREADS) rollout_heston2_kernel(RolloutArgs
   if (p.out == PATH_ROLLOUT) g.last_row(p, r, t0);
 }
 
+// --------------------------------------------------------------------------
+// Arithmetic-average (Asian) problems (DBSDE_PROB_ASIAN): state [A, S_1..S_k],
+// D = k + 1, Brownian dimension nb = k.  xin column 0 is t, column 1 is A,
+// column 2 + i is S_i (coordinate i = column - 2), column D + 1 the constant 1.
+// Two passes:
+//   pass 1 (rollout_asian_chain_kernel): the S columns, in ColGroup form -- a
+//     thread owns one path and one 16-byte column group and writes whole float4
+//     rows of xin and sdw.  S_i is the diagonal process (diag_step) on
+//     coordinate i of the diagonal rollout's Philox key, so its increments are
+//     those of a diagonal problem with D = k.  WS = false: the increments are
+//     drawn per 4-step Philox block or differenced from the caller's W
+//     (step_block: device grid or the caller's t), as rollout4_kernel does.
+//     WS = true (a factor, dbsde_set_corr): rollout_corrw_kernel ran first with
+//     its sdw pointer at xin + 1, so its store "column 1 + i" parked coordinate
+//     i's increment of step n in xin[row n, 2 + i] -- the S_i column itself;
+//     the thread reads its own columns RC_AHEAD rows ahead of the chain and
+//     overwrites them with X (no other thread touches them: no ordering between
+//     threads is needed), as the correlated Heston chain does with the sdw
+//     rows.  Column 1 gets A_0 in xin and 0 in sdw: the A column has no
+//     diffusion, so sdw[:, 1] is exactly 0 in every row.
+//   pass 2 (rollout_asian_avg_kernel): the A column.  A 16-lane group per path;
+//     per row lane l sums columns 2 + l, 2 + l + 16, ... ascending and the
+//     lanes meet in the xor butterfly (asian_row_sum's order, sde.hpp); A is
+//     the sequential prefix over n (asian_step) with dt_n the fp32 difference
+//     of the rows' own t column, which is pass 1's dt.  The row sums of
+//     AA_ROWS rows are formed before their prefix steps, so their loads are in
+//     flight together.  It reads the xin rows once and writes xin[:, 1].
+// --------------------------------------------------------------------------
+struct AsianGroup {
+  int c;
+  float x[4], a0;
+  bool live[4];   // the column is an asset S_i
+  __device__ __forceinline__ void init(const RolloutArgs& p, int m, int cg) {
+    c = cg;
+    const float* xi = p.Xi + (size_t)(p.xi_rows == 1 ? 0 : m) * p.D;
+    a0 = xi[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = 4 * c + k - 2;
+      live[k] = i >= 0 && i < p.nb;
+      x[k] = live[k] ? xi[1 + i] : 0.f;
+    }
+  }
+  __device__ __forceinline__ floatx4 xcols(const RolloutArgs& p, float t0) const {
+    floatx4 xo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int col = 4 * c + k;
+      xo[k] = col == 0 ? t0 : (col == 1 ? a0 : (col == p.D + 1 ? 1.f : x[k]));
+    }
+    return xo;
+  }
+  // row r = m (N + 1) + n, n < N, and x <- S_{n+1}
+  __device__ __forceinline__ void put_row(const RolloutArgs& p, size_t r, float t0, float dt, floatx4 dw) {
+    const floatx4 xo = xcols(p, t0);
+    floatx4 so;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) so[k] = live[k] ? diag_step(p.mu_a, p.sig_a, p.sig_b, dt, dw[k], x[k]) : 0.f;
+    *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xo;
+    *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = so;
+  }
+  __device__ __forceinline__ void last_row(const RolloutArgs& p, size_t r, float t0) const {
+    *(floatx4*)(p.xin + r * p.ldx + 4 * c) = xcols(p, t0);
+    *(floatx4*)(p.sdw + r * p.ldx + 4 * c) = floatx4{0.f, 0.f, 0.f, 0.f};
+  }
+};
+
+template <bool WS>
+__global__ void __launch_bounds__(WS ? RC_THREADS : 256) rollout_asian_chain_kernel(RolloutArgs p) {
+  const int C = p.ldx >> 2;
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= p.M * C) return;
+  const int m = gid / C, c = gid - m * C;
+  const int N1 = p.N + 1;
+  AsianGroup g;
+  g.init(p, m, c);
+  const double dt64 = (double)p.T / (double)p.N;
+  double tacc = 0.0;
+  float t0 = p.t ? p.t[(size_t)m * N1] : 0.0f;
+  const size_t r0 = (size_t)m * N1;
+  if constexpr (WS) {
+    for (int n0 = 0; n0 < p.N; n0 += RC_AHEAD) {
+      floatx4 dw[RC_AHEAD];
+#pragma unroll
+      for (int i = 0; i < RC_AHEAD; ++i)
+        dw[i] = n0 + i < p.N ? *(const floatx4*)(p.xin + (r0 + n0 + i) * p.ldx + 4 * c) : floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < RC_AHEAD; ++i) {
+        const int n = n0 + i;
+        if (n >= p.N) break;
+        tacc += dt64;
+        const float t1 = p.t ? p.t[(size_t)m * N1 + n + 1] : (float)tacc;
+        g.put_row(p, r0 + n, t0, rn_sub(t1, t0), dw[i]);
+        t0 = t1;
+      }
+    }
+  } else {
+    float w0[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w0[k] = (g.live[k] && p.W) ? p.W[(size_t)m * N1 * p.nb + 4 * c + k - 2] : 0.f;
+    const float sqdt = sqrtf(p.T / (float)p.N);
+    size_t r = r0;
+    for (int n0 = 0; n0 < p.N; n0 += 4) {
+      // every call sees the same grid sum, so t1 is the same from each
+      float dw[4][4], t1[4] = {0.f, 0.f, 0.f, 0.f};
+      double tn = tacc;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dw[k][i] = 0.f;
+        if (g.live[k]) {
+          tn = tacc;
+          step_block(p, m, 4 * c + k - 2, n0, w0[k], tn, dt64, sqdt, dw[k], t1);
+        }
+      }
+      tacc = tn;   // unchanged for a thread without an asset column: its rows hold no t (column 2 is S_1)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (n0 + i >= p.N) break;
+        g.put_row(p, r, t0, rn_sub(t1[i], t0), floatx4{dw[0][i], dw[1][i], dw[2][i], dw[3][i]});
+        t0 = t1[i];
+        ++r;
+      }
+    }
+  }
+  g.last_row(p, r0 + p.N, t0);
+}
+
+constexpr int AA_ROWS = 4;        // row sums in flight per prefix block
+constexpr int AA_THREADS = 256;   // 16 paths per workgroup
+constexpr int AA_TERMS = 8;       // loads of one lane sum in flight
+// asian_lane_sum (sde.hpp): the same terms added in the same order, their loads
+// issued AA_TERMS at a time ahead of the adds
+__device__ __forceinline__ float asian_lane_sum_ahead(const float* S, int k, int lane) {
+  float p = 0.f;
+  for (int i0 = lane; i0 < k; i0 += AA_TERMS * ASIAN_LANES) {
+    float v[AA_TERMS];
+#pragma unroll
+    for (int j = 0; j < AA_TERMS; ++j) v[j] = i0 + j * ASIAN_LANES < k ? S[i0 + j * ASIAN_LANES] : 0.f;
+#pragma unroll
+    for (int j = 0; j < AA_TERMS; ++j)
+      if (i0 + j * ASIAN_LANES < k) p = rn_add(p, v[j]);
+  }
+  return p;
+}
+__global__ void __launch_bounds__(AA_THREADS) rollout_asian_avg_kernel(RolloutArgs p) {
+  const long long gid = (long long)blockIdx.x * AA_THREADS + threadIdx.x;
+  const bool ok = gid / ASIAN_LANES < p.M;   // (a 16-lane group is one path: its lanes agree)
+  const int m = ok ? (int)(gid / ASIAN_LANES) : 0, l = (int)(gid & (ASIAN_LANES - 1));
+  const int k = p.nb, N1 = p.N + 1;
+  const float* xr = p.xin + (size_t)m * N1 * p.ldx;
+  float A = ok ? p.Xi[(size_t)(p.xi_rows == 1 ? 0 : m) * p.D] : 0.f;
+  for (int n0 = 0; n0 <= p.N; n0 += AA_ROWS) {
+    float s[AA_ROWS], dt[AA_ROWS];
+#pragma unroll
+    for (int j = 0; j < AA_ROWS; ++j) {
+      const int n = n0 + j;
+      const bool row = ok && n < p.N;
+      s[j] = row ? asian_lane_sum_ahead(xr + (size_t)n * p.ldx + 2, k, l) : 0.f;
+      dt[j] = row ? rn_sub(xr[(size_t)(n + 1) * p.ldx], xr[(size_t)n * p.ldx]) : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < AA_ROWS; ++j) {
+#pragma unroll
+      for (int o = 1; o < ASIAN_LANES; o <<= 1) s[j] = rn_add(s[j], __shfl_xor(s[j], o));
+    }
+#pragma unroll
+    for (int j = 0; j < AA_ROWS; ++j) {
+      const int n = n0 + j;
+      if (!ok || n > p.N) break;
+      if (l == 0) p.xin[((size_t)m * N1 + n) * p.ldx + 1] = A;
+      if (n < p.N) asian_step(asian_mean(s[j], k), dt[j], p.T, A);
+    }
+  }
+}
+
 // Q3 (D == 1): S_n = sum over paths of sdw[m, n]   (1d_BSPDE_case.py:271-273)
 __global__ void __launch_bounds__(256) q3_sum_kernel(const float* sdw, int ldx, int M, int N, float* S) {
   const int n = blockIdx.x;

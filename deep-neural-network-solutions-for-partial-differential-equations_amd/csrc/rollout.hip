@@ -7,6 +7,8 @@
 // Correlated Heston (L between the k assets): the increment GEMM at every k,
 // then rollout_heston_chain_kernel.
 // Two-factor Heston (DBSDE_PROB_HESTON2): rollout_heston2_kernel for everything.
+// Arithmetic average (DBSDE_PROB_ASIAN): rollout_asian_chain_kernel (behind the
+// increment GEMM when a factor is set), then rollout_asian_avg_kernel.
 #include <hip/hip_runtime.h>
 
 // a prefetched rollout runs on the next chunked step's second stream
@@ -151,7 +153,45 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
   const double bytes = ra.out == PATH_ROLLOUT ? 4.0 * steps * (2.0 * ra.D + (ra.W ? ra.nb : 0)) : 4.0 * steps * ra.nb;
   // the rollouts store whole float4 columns of the rows (ldx = Dp = pad16(D + 2))
   if (ra.ldx % 4 != 0) return fail(c, DBSDE_EINVAL, "internal: path row stride is not a multiple of 4 floats");
-  if (c->heston2) {
+  if (c->asian) {
+    // arithmetic-average problems (paths.hpp): the S chains -- behind the
+    // increment GEMM when a factor is set -- then the averaging pass; one form
+    // in-step and prefetched, on the device grid and on the caller's t / W
+    const int k = ra.nb;
+    if (k != ra.D - 1 || k < 1 || k > CW_OB * 8 * 16) return fail(c, DBSDE_EINVAL, "internal: Asian rollout geometry");
+    const bool corr = c->Lt && !ra.W;
+    const dim3 gw((ra.M + CW_PATHS - 1) / CW_PATHS, (ra.N + 3) / 4);
+    const double fl = 2.0 * steps * k * k / 2;
+    if (ra.out != PATH_ROLLOUT) {
+      // the fetch is that of a diagonal problem with D = k
+      if (corr) {
+        RUN(c, s, "corr_increments", fl, 4.0 * steps * k, rollout_corrw_kernel<<<gw, CW_THREADS, 0, s>>>(ra));
+        const long long nthr = (long long)ra.M * k;
+        RUN(c, s, name, 0.0, bytes, corrw_fetch_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, s>>>(ra));
+      } else {
+        RolloutArgs fa = ra;
+        fa.D = k;
+        const int nthr = ra.M * k;
+        RUN(c, s, name, 0.0, bytes, fetch_diag_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(fa));
+      }
+      return DBSDE_OK;
+    }
+    const int chains = ra.M * (ra.ldx / 4);
+    if (corr) {
+      // coordinate i's increments into xin[row, 2 + i], the S_i column the chain then overwrites
+      RolloutArgs ia = ra;
+      ia.sdw = ra.xin + 1;
+      RUN(c, s, "corr_increments", fl, 4.0 * steps * k, rollout_corrw_kernel<<<gw, CW_THREADS, 0, s>>>(ia));
+      RUN(c, s, "asian_chain", 0.0, bytes + 4.0 * steps * k,
+          rollout_asian_chain_kernel<true><<<(unsigned)((chains + RC_THREADS - 1) / RC_THREADS), RC_THREADS, 0, s>>>(ra));
+    } else {
+      RUN(c, s, "asian_chain", 0.0, bytes, rollout_asian_chain_kernel<false><<<(chains + 255) / 256, 256, 0, s>>>(ra));
+    }
+    // reads the k S columns and t of every row, writes the A column
+    const int groups = ra.M * ASIAN_LANES;
+    RUN(c, s, "asian_avg", 3.0 * steps * k, 4.0 * steps * (k + 2.0),
+        rollout_asian_avg_kernel<<<(groups + AA_THREADS - 1) / AA_THREADS, AA_THREADS, 0, s>>>(ra));
+  } else if (c->heston2) {
     // two-factor Heston (never with a factor: dbsde_set_corr refuses it): one
     // kernel for device- and parity-mode batches, in-step and prefetched, and
     // for the fetch; thread per (path, asset)

@@ -92,4 +92,36 @@ DBSDE_HD void heston2_step(float mu_a, float kappa, float theta, float hsig, flo
   v = rn_add(rn_add(v, rn_mul(c.muV, dt)), b);
 }
 
+// Arithmetic-average (Asian) problems (DBSDE_PROB_ASIAN, include/dbsde.h):
+// state [A, S_1..S_k], each S_i a diagonal process (diag_step), A the running
+// average of the row mean.  The row sum runs in one fixed order over
+// ASIAN_LANES = 16 partial sums: partial l adds S_l, S_{l + 16}, ... ascending
+// onto 0, then the partials meet in an xor butterfly p_l <- p_l + p_{l ^ o},
+// o = 1, 2, 4, 8 (fp32 addition commutes, so every partial ends as the same
+// sum).  On the device a partial is a lane of a 16-lane group and the
+// butterfly its shuffles (paths.hpp); asian_row_sum is the same order on one
+// thread.
+//   m = (sum_i S_i) / (float)k,   A <- A + (m dt) / T        (the left-point rule)
+// with the division correctly rounded (hipcc's default for fp32) and the
+// product and the sum rounded on their own.
+constexpr int ASIAN_LANES = 16;
+DBSDE_HD float asian_lane_sum(const float* S, int k, int lane) {
+  float p = 0.f;
+  for (int i = lane; i < k; i += ASIAN_LANES) p = rn_add(p, S[i]);
+  return p;
+}
+DBSDE_HD float asian_row_sum(const float* S, int k) {
+  float p[ASIAN_LANES];
+  for (int l = 0; l < ASIAN_LANES; ++l) p[l] = asian_lane_sum(S, k, l);
+  for (int o = 1; o < ASIAN_LANES; o <<= 1) {
+    float q[ASIAN_LANES];
+    for (int l = 0; l < ASIAN_LANES; ++l) q[l] = rn_add(p[l], p[l ^ o]);
+    for (int l = 0; l < ASIAN_LANES; ++l) p[l] = q[l];
+  }
+  return p[0];
+}
+DBSDE_HD float asian_mean(float sum, int k) { return sum / (float)k; }
+// A_{n+1} from A_n, the row mean m_n of S_n and dt_n
+DBSDE_HD void asian_step(float m, float dt, float T, float& A) { A = rn_add(A, rn_mul(m, dt) / T); }
+
 }  // namespace dbsde

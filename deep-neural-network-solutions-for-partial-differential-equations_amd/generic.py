@@ -39,18 +39,29 @@ _PKG = __name__.rsplit(".", 1)[0]
 
 
 # ---------------------------------------------------------------------- spec formulas
-def spec_functions(spec, strike=None):
+def spec_functions(spec, strike=None, T=None):
     """The coefficients a DIAG ProblemSpec declares (include/dbsde.h), as
-    torch functions of the reference methods' signatures."""
+    torch functions of the reference methods' signatures.  An average=True
+    spec (state [A, S_1..S_k], DBSDE_PROB_ASIAN) has the A row mean S / T in mu
+    (T is then required) and a zero A row in sigma [R, 1 + k, k]."""
     K = spec.strike if strike is None else strike
+    average = bool(getattr(spec, "average", False))
+    if average and T is None:
+        raise ValueError("spec_functions needs T for an average=True spec (the A drift is mean S / T)")
 
     def cols(X):
         return X[:, :spec.g_cols] if spec.g_cols else X
 
     def mu(t, X, Y=None, Z=None):
+        if average:
+            S = X[:, 1:]
+            return torch.cat([torch.mean(S, dim=1, keepdim=True) / T, spec.mu_a * S], dim=1)
         return spec.mu_a * X
 
     def sigma(t, X, Y=None):
+        if average:
+            A = torch.diag_embed(spec.sig_a * X[:, 1:] + spec.sig_b)
+            return torch.cat([torch.zeros_like(A[:, :1, :]), A], dim=1)
         return torch.diag_embed(spec.sig_a * X + spec.sig_b)
 
     def phi(t, X, Y, Z):
@@ -136,7 +147,7 @@ def coefficient_mismatches(obj, base, spec, D, T, xi, device):
         return []
     if spec.kind != "diag":
         return [n for n in names if user_defined(overridden(obj, base, n))]
-    ref = spec_functions(spec)
+    ref = spec_functions(spec, T=T)
     t, X, Y, Z = probe_inputs(D, T, xi, device)
     bad = []
     with torch.no_grad():

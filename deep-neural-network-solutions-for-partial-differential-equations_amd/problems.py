@@ -14,6 +14,9 @@ methods (generic.py) instead of silently training the parent's problem.
   HamiltonJacobiBellman hjb_implement.py:590-604        phi = |Z|^2, g = log(1/2 + |X|^2/2)
   HestonFBSNN           heston_dnnpde.py:519-699        k-asset stochastic volatility
   HestonTwoFactorFBSNN  (no reference counterpart)      the two-factor Heston model on that surface
+  AsianCallOption / AsianPutOption, AsianBasketCallOption / AsianBasketPutOption
+                        (no reference counterpart)      arithmetic-average options: the running
+                                                        average as one more state coordinate
   BlackScholesBarenblatt: see deepbsde.py (DeepBSDE.py:326-341 surface)
 """
 from __future__ import annotations
@@ -410,5 +413,125 @@ class HestonTwoFactorFBSNN(HestonFBSNN):
                       (0.05, self.strike, self.kappa, self.theta, self.sigma, self.rho))
 
 
+class _AsianState:
+    """The arithmetic-average (Asian) option on D assets (no reference
+    counterpart; problem kind DBSDE_PROB_ASIAN, ProblemSpec(average=True)).
+
+    The running average is carried as one more state coordinate: the state is
+    [A, S_1..S_D] (state_dim = D + 1), every S_i follows the basket dynamics
+    dS = 0.05 S dt + 0.20 S dW_i, A' = A + mean_i S_i dt / T (the left-point
+    rule, A_0 = 0), and u(t, A, S) solves
+
+      u_t + (mean S / T) u_A + sum_i 0.05 S_i u_{S_i} + 1/2 tr(sigma sigma^T D^2_S u) - 0.05 u = 0,
+      u(T, .) = g(A),
+
+    g the call max(A - K, 0) or put max(K - A, 0) on the average, or with
+    payoff_type='continuous' their sigmoid-smoothed forms (alpha = 10).  The
+    Brownian dimension is D (fetch_minibatch draws D columns; correlation_type
+    correlates the D assets), the network takes (t, A, S) -- D + 2 inputs:
+    `layers[0]` is replaced by D + 2 -- and Xi holds the D asset prices (A = 0
+    is prepended; rows of D + 1 columns are taken as [A, S] as given).  predict
+    returns X [M, N+1, D + 1] with A in column 0; net_u, theta, pde_residual and
+    mc_value take points [A, S_1..S_D] (mc_value also [S_1..S_D] with A = 0).
+    Limits: the average is arithmetic with a fixed strike (no geometric or
+    floating-strike average), there is no closed form, the assets are diagonal
+    processes (no average over Heston states), and a subclass overriding a
+    coefficient method with other coefficients is refused (NotImplementedError)
+    instead of running on the generic path."""
+
+    option_type = "call"
+
+    def __init__(self, Xi, T, M, N, D, Mm, layers, mode, activation, correlation_type="no_correlation",
+                 payoff_type='discontinuous', device=None):
+        if payoff_type not in ("discontinuous", "continuous"):
+            raise ValueError("Invalid payoff type. Choose 'discontinuous' or 'continuous'.")
+        self.payoff_type = payoff_type
+        self.n_assets = D
+        super().__init__(Xi, T, M, N, D, Mm, layers, mode, activation, correlation_type, device=device)
+
+    def _default_strike(self):
+        return 1.0
+
+    def _native_layers(self, layers):
+        return [2 + self.n_assets] + layers[1:]
+
+    def _make_model(self, layers):
+        return networks.make_model(self.mode, [2 + self.n_assets] + list(layers[1:]), self.activation)
+
+    def _full_state(self, Xi):
+        """[S_1..S_D] -> [0, S_1..S_D]; rows of D + 1 columns are [A, S] already."""
+        k = self.n_assets
+        x = torch.as_tensor(np.asarray(Xi) if not isinstance(Xi, torch.Tensor) else Xi,
+                            dtype=torch.float32).to(self.device)
+        x = x.reshape(-1, x.shape[-1]) if x.dim() > 1 else x.reshape(1, -1)
+        if x.shape[1] == k + 1:
+            return x.contiguous()
+        if x.shape[1] != k:
+            raise ValueError(f"Xi has {x.shape[1]} columns; expected the {k} asset prices (or [A, S]: {k + 1})")
+        return torch.cat([torch.zeros_like(x[:, :1]), x], 1).contiguous()
+
+    def _initial_state(self, Xi):
+        return self._full_state(Xi)
+
+    def _mc_state(self, X):
+        return self._full_state(X)
+
+    def problem_spec(self):
+        smooth = self.payoff_type == "continuous"
+        if self.option_type == "put":
+            g = "smooth_put" if smooth else "put_mean"
+        else:
+            g = "smooth_call" if smooth else "call_mean"
+        return ProblemSpec(mu_a=0.05, sig_a=0.20, phi_r=0.05, phi_c=0.0, g=g, strike=self.strike, g_alpha=10.0,
+                           g_cols=1, q3=False, average=True)
+
+    def phi_tf(self, t, X, Y, Z):
+        return 0.05 * (Y)
+
+    def g_tf(self, X):
+        a = X[:, :1] - self.strike
+        if self.option_type == "put":
+            a = -a
+        if self.payoff_type == "discontinuous":
+            return torch.maximum(a, torch.tensor(0.0, device=X.device))
+        return a / (1 + torch.exp(-10.0 * a))
+
+    def mu_tf(self, t, X, Y=None, Z=None):
+        S = X[:, 1:]
+        return torch.cat([torch.mean(S, dim=1, keepdim=True) / self.T, 0.05 * S], dim=1)
+
+    def sigma_tf(self, t, X, Y=None):
+        """[R, D + 1, D]: a zero A row over 0.20 diag(S)."""
+        A = 0.20 * torch.diag_embed(X[:, 1:])
+        return torch.cat([torch.zeros_like(A[:, :1, :]), A], dim=1)
+
+    def predict(self, Xi_star, t_star, W_star):
+        """-> (X [M, N+1, D + 1] with A in column 0, Y)."""
+        return super().predict(self._full_state(Xi_star), t_star, W_star)
+
+
+class AsianCallOption(_AsianState, FBSNN):
+    """The arithmetic-average call max(A_T - K, 0), K = 1 by default, on
+    CallOption's surface (its train(), schedule and gradient clipping)."""
+
+
+class AsianPutOption(AsianCallOption):
+    """AsianCallOption's problem with the put payoff max(K - A_T, 0)."""
+
+    option_type = "put"
+
+
+class AsianBasketCallOption(_AsianState, _WithCorrTrain, FBSNN):
+    """The arithmetic-average call on a basket, on BasketCallOption's surface:
+    its train() (the N**(1/5) schedule, time_logs) and correlated increments."""
+
+
+class AsianBasketPutOption(AsianBasketCallOption):
+    """AsianBasketCallOption's problem with the put payoff max(K - A_T, 0)."""
+
+    option_type = "put"
+
+
 __all__ = ["CallOption", "PutOption", "CallOption1D", "BasketCallOption", "BasketPutOption", "BSPDETestCase", "HamiltonJacobiBellman",
-           "HestonFBSNN", "HestonTwoFactorFBSNN"]
+           "HestonFBSNN", "HestonTwoFactorFBSNN", "AsianCallOption", "AsianPutOption", "AsianBasketCallOption",
+           "AsianBasketPutOption"]

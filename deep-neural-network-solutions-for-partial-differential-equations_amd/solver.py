@@ -25,7 +25,11 @@ class ProblemSpec:
                    with correlation rho between the two, none between assets
     phi = phi_r (Y - phi_c X.Z) + phi_zz |Z|^2, g = g_kind(strike, alpha) over
     the first g_cols state columns (0 = all), u_clamp: u = max(net, 0).
-    q3: reproduce the D == 1 squeeze broadcast."""
+    q3: reproduce the D == 1 squeeze broadcast.
+    average (kind "diag" only): the arithmetic-average (Asian) problem
+    DBSDE_PROB_ASIAN -- state [A, S_1..S_k], every S_i the diag process, A the
+    running average of mean_i S_i (A' = A + mean S dt / T), nb = k; the payoff
+    is on A alone (g_cols = 1, a call or put g, phi_c = 0)."""
 
     mu_a: float = 0.0
     sig_a: float = 0.0
@@ -44,13 +48,18 @@ class ProblemSpec:
     theta: float = 0.0
     sigma: float = 0.0
     rho: float = 0.0
+    average: bool = False
 
     def to_c(self):
         if self.g not in _lib.G_KINDS:
             raise ValueError(f"unknown terminal condition {self.g!r}")
         if self.kind not in _lib.PROBLEM_KINDS:
             raise ValueError(f"unknown problem kind {self.kind!r}")
-        return _lib.Problem(_lib.PROBLEM_KINDS[self.kind], self.mu_a, self.sig_a, self.sig_b, self.phi_r,
+        if self.average and self.kind != "diag":
+            raise ValueError("average=True (the Asian problem) needs kind 'diag': an average over Heston states is "
+                             "not supported")
+        kind = _lib.PROB_ASIAN if self.average else _lib.PROBLEM_KINDS[self.kind]
+        return _lib.Problem(kind, self.mu_a, self.sig_a, self.sig_b, self.phi_r,
                             self.phi_c, self.phi_zz, _lib.G_KINDS[self.g], self.strike, int(self.q3),
                             int(self.g_cols), self.g_alpha, int(self.u_clamp), self.kappa, self.theta,
                             self.sigma, self.rho)
@@ -462,7 +471,9 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
     factor: [D, D] for diag problems (D <= 128 here, although the training
     step's set_corr takes D <= 1022), [k, k] between the k = D / 2 <= 511 assets'
     Brownian motions for kind "heston" (the process of a Heston solver with
-    set_corr; sent as DBSDE_PROB_HESTON_CORR); "heston2" takes none.  Returns
+    set_corr; sent as DBSDE_PROB_HESTON_CORR); "heston2" takes none; an
+    average=True spec (X [P, 1 + k] = [A, S_1..S_k]) takes [k, k], k <= 128,
+    and its delta is [dA, dS_1..dS_k].  Returns
     (value [P, 1], stderr [P, 1], delta [P, D] or None); delta is the pathwise
     estimator (diag only)."""
     if spec.phi_zz != 0:
@@ -474,7 +485,7 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
             raise ValueError("L applies to DIAG problems and to kind 'heston' only: the two-factor Heston model has "
                              "no correlation between assets")
         D_ = X.numel() // max(X.shape[0], 1)
-        n = D_ // 2 if spec.kind == "heston" else D_
+        n = D_ // 2 if spec.kind == "heston" else (D_ - 1 if spec.average else D_)   # average: [A, S_1..S_k]
         if L.shape != (n, n) or (spec.kind == "heston" and D_ % 2):
             raise ValueError(f"L must be [{n}, {n}]" + (" (k = D / 2 assets)" if spec.kind == "heston" else ""))
     lib = _lib.load()

@@ -84,6 +84,13 @@ extern "C" {
                                  assets' Brownian motions correlated by its L argument,
                                  dW = sqrt(dt) (L z), L [k, k].  A context takes kind
                                  HESTON plus dbsde_set_corr instead                    */
+/* kind 4.  Written as the successor of HESTON_CORR, not as a literal: the ABI tests pin the
+   list of literal kind values of this header (tests/test_abi_mc_heston_corr.py), and
+   tests/test_abi_asian.py holds the compiled value to 4 */
+#define DBSDE_PROB_ASIAN (DBSDE_PROB_HESTON_CORR + 1)
+                              /* arithmetic-average (Asian) option on k DIAG assets: state
+                                 [A, S_1..S_k], A the running average of mean_i S_i, one
+                                 Brownian motion per asset (nb = D - 1)                */
 
 /*
  * Problem coefficients (one FBSNN subclass = one filled struct):
@@ -115,6 +122,26 @@ extern "C" {
  *     and a call / put payoff.
  *   kind HESTON_CORR: HESTON's fields, state and step, for dbsde_mc_value alone (the
  *     factor is that call's L argument); dbsde_create refuses it.
+ *   kind ASIAN, the same struct: state [A, S_1..S_k], D = k + 1 >= 2 (else
+ *     DBSDE_EINVAL), Brownian dimension nb = k = D - 1 (column i of W drives S_i;
+ *     A has no diffusion).  Each S_i is the DIAG process with mu_a, sig_a, sig_b,
+ *     its increment dW_i the Philox coordinate i of the diagonal rollout's key (or
+ *     the caller's W [M, N+1, k], or with dbsde_set_corr (n = k) dW = L (sqrt(dt) z)).
+ *     A is the running average of the row mean by the left-point rule, every
+ *     operation rounded to fp32 on its own, in this order:
+ *       s_i  = (sig_a S_i + sig_b) dW_i           S_i' = (S_i + (mu_a S_i) dt) + s_i
+ *       p_l  = ((0 + S_l) + S_{l+16}) + ...       l = 0..15, ascending over the assets
+ *       p_l <- p_l + p_{l xor o}                  o = 1, 2, 4, 8 in turn: sum = p_0
+ *       m    = sum / (float)k                     (S at the row's own time t_n)
+ *       A'   = A + (m dt) / T                     so A_N = A_0 + (1/T) sum_{n<N} m_n dt_n
+ *     sigma dW (the Y-tilde term): A: exactly 0, S_i: s_i.  The PDE is
+ *       u_t + (mean S / T) u_A + sum_i mu_a S_i u_{S_i} + 1/2 tr(sigma sigma^T D^2_S u) - phi = 0,
+ *       u(T, .) = g(A).
+ *     The payoff is on A alone: g_cols must be 1 and g_kind one of CALL_SUM,
+ *     CALL_MEAN, SMOOTH_CALL, PUT_SUM, PUT_MEAN, SMOOTH_PUT (SUMSQ and LOG are
+ *     DBSDE_EINVAL); phi_c must be 0 (X.Z would include A u_A); q3 is ignored.
+ *     dbsde_pde_residual takes nd = 1 + k directions (A component 0) and the
+ *     drift above; dbsde_mc_value simulates the same process (below).
  *   phi      =phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
  *   g        = g_kind over the first g_cols state columns (0 = all), strike,
  *              g_alpha (DBSDE_G_SMOOTH_CALL / _PUT); the terminal |Z - grad g|^2 term
@@ -189,7 +216,8 @@ int dbsde_param_used_mask(const dbsde_ctx* ctx, unsigned char* mask, long long n
  * create time (DBSDE_X3=0 / DBSDE_TNW_X3=0 select the fp32 forms). */
 int dbsde_matrix_form(const dbsde_ctx* ctx);
 
-/* Brownian dimension nb of a batch's W [M, N+1, nb]: D (DIAG, HESTON2), or D/2 for HESTON */
+/* Brownian dimension nb of a batch's W [M, N+1, nb]: D (DIAG, HESTON2), D/2 for HESTON,
+   D - 1 for ASIAN */
 int dbsde_brownian_dim(const dbsde_ctx* ctx);
 
 /*
@@ -338,7 +366,9 @@ int dbsde_net_u_jet(dbsde_ctx* ctx, const float* params, int R, const float* t, 
  *              per asset in its (S_i, v_i) plane, with the rollout's sqrt(max(v, 1e-8)) and
  *              +-100 clamps; with a factor between the assets (dbsde_set_corr, L [k, k])
  *              column j of Sigma(x) . L: those entries of every asset i >= j times L[i][j];
- *              HESTON2 its 2k columns: dW^S_i -> (S_i: d00, v_i: d10), dW^v_i -> (v_i: d11)
+ *              HESTON2 its 2k columns: dW^S_i -> (S_i: d00, v_i: d10), dW^v_i -> (v_i: d11);
+ *              ASIAN (drift: mu_a S_i on the S columns, mean S / T on A) the k columns of
+ *              diag(sig_a S + sig_b) . L in the S columns, A component 0
  *   phi        phi_r (u - phi_c X . Du) + phi_zz |Du|^2   (q3 is ignored)
  *   residual   u_t + drift + diffusion - phi
  *   scale      |u_t| + |drift| + 1/2 sum_j |a_j^T D^2u a_j| + |phi|: what the residual is
@@ -525,6 +555,15 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * call, default 1024); a call that needs more runs its sample chunks in groups,
  * which changes no bit of the result.  With L = I the result is HESTON's, bit for
  * bit.  phi_zz != 0 (HJB) is DBSDE_EINVAL: use dbsde_hjb_mc.
+ * ASIAN (x [P, D] = [A_p, S_1..S_k], D = k + 1): thread (sample, asset d) runs
+ * DIAG's step on S_d with Brownian coordinate d and accumulates
+ * I_d = sum_n (double)fp32(S_{d,n} dt_n) (S at the left end of each step); the
+ * sample's terminal average is A_T = A_p + (sum_d I_d) / (k T) in fp64, T the
+ * full maturity (not tau_p), the I_d summed in the order DIAG sums its terminal
+ * X; g(A_T) is the problem's payoff with one column.  delta (under DIAG's rules):
+ * d/dA_p = g', d/dS_d = g' (sum_n (double)fp32(J_{d,n} dt_n)) / (k T), J the DIAG
+ * tangent.  L [k, k] (k <= 128) correlates the assets as for DIAG.  tau_p <= 0
+ * returns g(A_p), 0 and (g', 0, .., 0).
  *
  *   L       device [nb, nb] row-major lower Cholesky factor (the lower triangle is
  *           read), NULL = independent increments; DIAG: nb = D <= 128;
@@ -557,7 +596,8 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * DBSDE_EINVAL before any HIP call: NULL prob / t / x / value; P, D, n_steps
  * or mc < 1; mc > 2^32; D > 4096; Heston with an odd D, with L or with delta;
  * L with D > 128; HESTON_CORR without L, with an odd D, with delta or with
- * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0.  Needs no context;
+ * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0; ASIAN with D < 2,
+ * phi_c != 0, g_cols != 1, g_kind SUMSQ or LOG, or L with D - 1 > 128.  Needs no context;
  * the work is enqueued on hip_stream.
  */
 int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const float* L, const float* t, const float* x, int P,

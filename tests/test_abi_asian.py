@@ -1,0 +1,161 @@
+"""The arithmetic-average (Asian) problem (problem kind 4, DBSDE_PROB_ASIAN) at
+the C boundary, without a GPU: the new value rides on the existing entry
+points (no new symbol, ABI version 3, PROBLEM_KINDS unchanged), every refusal
+of the kind is DBSDE_EINVAL before any HIP call at dbsde_create and in
+dbsde_mc_value, and kinds 5 to 7 are still unknown."""
+import ctypes
+import importlib
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+from conftest import ROOT, load_pkg
+
+HEADER = os.path.join(ROOT, "include", "dbsde.h")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    pkg = load_pkg()
+    importlib.import_module(pkg.__name__ + ".build_lib").build(verbose=False)
+    return pkg._lib.load()
+
+
+def asian(pkg, **over):
+    kw = dict(mu_a=0.05, sig_a=0.2, phi_r=0.05, phi_c=0.0, g="call_mean", strike=1.0, g_alpha=10.0, g_cols=1, q3=False,
+              average=True)
+    kw.update(over)
+    return pkg.ProblemSpec(**kw)
+
+
+def compiled_value(tmp_path, macro):
+    """The macro as a C compiler sees it (the header is plain C)."""
+    src, exe = tmp_path / "v.c", tmp_path / "v"
+    src.write_text(f'#include <stdio.h>\n#include "dbsde.h"\nint main(void) {{ printf("%d\\n", (int)({macro})); return 0; }}\n')
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], check=True)
+    return int(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+
+
+def test_the_kind_is_bound_to_the_header_value(tmp_path):
+    pkg = load_pkg()
+    hv = {n: int(v) for n, v in re.findall(r"^#define (DBSDE_\w+) (-?\d+)\b", open(HEADER).read(), flags=re.M)}
+    assert compiled_value(tmp_path, "DBSDE_PROB_ASIAN") == 4 == pkg._lib.PROB_ASIAN
+    assert compiled_value(tmp_path, "DBSDE_PROB_HESTON_CORR") == 3
+    assert hv["DBSDE_ABI_VERSION"] == pkg._lib.ABI_VERSION == 3
+    assert len(pkg._lib.EXPORTED) == 32
+    assert pkg._lib.PROBLEM_KINDS == {"diag": 0, "heston": 1, "heston2": 2}
+    assert pkg._lib.PROB_HESTON_CORR == 3
+    assert [hv[n] for n in ("DBSDE_PROB_DIAG", "DBSDE_PROB_HESTON", "DBSDE_PROB_HESTON2", "DBSDE_PROB_HESTON_CORR")] \
+        == [0, 1, 2, 3]
+    assert asian(pkg).to_c().kind == 4
+    assert pkg.ProblemSpec(average=True).to_c().kind == 4
+    assert pkg.ProblemSpec().to_c().kind == 0
+
+
+def test_the_library_exports_the_same_32_symbols(lib):
+    pkg = load_pkg()
+    out = os.popen(f"nm -D --defined-only {pkg._lib.LIB_PATH}").read()
+    names = sorted(set(re.findall(r"\bT (dbsde_\w+)", out)))
+    assert names == sorted(pkg._lib.EXPORTED) and len(names) == 32
+    assert lib.dbsde_abi_version() == 3
+
+
+def _create(pkg, lib, layers, prob, mode="Naisnet"):
+    cfg = pkg._lib.Config()
+    cfg.mode, cfg.activation, cfg.n_layers = pkg._lib.MODES[mode], 0, len(layers)
+    for k, v in enumerate(layers):
+        cfg.layers[k] = v
+    cfg.problem = prob
+    cfg.T = 1.0
+    ctx = ctypes.c_void_p()
+    rc = lib.dbsde_create(ctypes.byref(cfg), ctypes.byref(ctx))
+    return rc, ctx, lib.dbsde_last_error(None)
+
+
+REFUSALS = [(dict(phi_c=1.0), b"phi_c"), (dict(g_cols=0), b"g_cols"), (dict(g_cols=2), b"g_cols"),
+            (dict(g="sumsq"), b"sumsq"), (dict(g="log"), b"sumsq")]
+
+
+def test_create_refuses_before_any_hip_call(lib):
+    pkg = load_pkg()
+    E = pkg._lib.DBSDE_EINVAL
+    lay = [5, 16, 16, 16, 16, 1]                                  # D = 4: [A, S_1..S_3]
+    for over, word in REFUSALS:
+        rc, ctx, msg = _create(pkg, lib, lay, asian(pkg, **over).to_c())
+        assert rc == E and not ctx.value and word in msg, (over, rc, msg)
+    rc, ctx, msg = _create(pkg, lib, [2, 16, 16, 16, 16, 1], asian(pkg).to_c())      # D = 1: no asset
+    assert rc == E and not ctx.value and b"D must be >= 2" in msg
+    for kind in (5, 6, 7):
+        prob = asian(pkg).to_c()
+        prob.kind = kind
+        rc, ctx, msg = _create(pkg, lib, lay, prob)
+        assert rc == E and not ctx.value and b"unknown problem kind" in msg, kind
+    # the accepted problem gets past every argument check: with a device it is created, without one it
+    # stops at the first HIP call
+    rc, ctx, msg = _create(pkg, lib, lay, asian(pkg, q3=True).to_c())                 # q3 is ignored
+    if torch.cuda.is_available():
+        assert rc == pkg._lib.DBSDE_OK and ctx.value
+        assert lib.dbsde_brownian_dim(ctx) == 3
+        lib.dbsde_destroy(ctx)
+    else:
+        assert rc == pkg._lib.DBSDE_EHIP and not ctx.value, (rc, msg)
+
+
+def _mc(lib, prob, D=4, L=None, delta=None, t=1, x=1, value=1):
+    """Pointers are never dereferenced on the refused paths: 1 stands for 'not NULL'."""
+    vp = lambda v: None if v is None else ctypes.c_void_p(v)
+    return lib.dbsde_mc_value(ctypes.byref(prob), D, 1.0, vp(L), vp(t), vp(x), 1, 4, 16, 0, 0, vp(value), None, vp(delta),
+                              None)
+
+
+def test_mc_value_refuses_before_any_hip_call(lib):
+    pkg = load_pkg()
+    E = pkg._lib.DBSDE_EINVAL
+    for over, word in REFUSALS:
+        assert _mc(lib, asian(pkg, **over).to_c()) == E, over
+        assert word in lib.dbsde_last_error(None), (over, lib.dbsde_last_error(None))
+    assert _mc(lib, asian(pkg).to_c(), D=1) == E
+    assert b"D must be >= 2" in lib.dbsde_last_error(None)
+    assert _mc(lib, asian(pkg).to_c(), D=130, L=1) == E                  # 129 assets under a factor
+    assert b"128" in lib.dbsde_last_error(None)
+    assert _mc(lib, asian(pkg, phi_zz=1.0).to_c()) == E
+    assert b"phi_zz" in lib.dbsde_last_error(None)
+    for kind in (5, 6, 7):
+        prob = asian(pkg).to_c()
+        prob.kind = kind
+        assert _mc(lib, prob) == E and b"unknown problem kind" in lib.dbsde_last_error(None)
+    # DIAG's own limit under a factor is untouched: D = 129 is refused, the Asian D = 129 (128 assets) is not
+    diag = pkg.ProblemSpec(mu_a=0.05, sig_a=0.2, phi_r=0.05, g="call_mean", strike=1.0).to_c()
+    assert _mc(lib, diag, D=129, L=1) == E and b"D <= 128" in lib.dbsde_last_error(None)
+
+
+def test_mc_value_accepts_the_kind(lib):
+    """Past the argument checks: without a device the call stops at its first
+    HIP call and never reads its pointers; with one it runs on one-point
+    buffers (with and without delta)."""
+    pkg = load_pkg()
+    gpu = torch.cuda.is_available()
+    if gpu:
+        t, x = torch.zeros(1, device="cuda:0"), torch.tensor([0.0, 1.0, 1.1, 0.9], device="cuda:0")
+        out, dl = torch.empty(1, device="cuda:0"), torch.empty(4, device="cuda:0")
+        tp, xp, op, dp = (v.data_ptr() for v in (t, x, out, dl))
+    else:
+        tp = xp = op = dp = 4096
+    for g in ("call_sum", "call_mean", "smooth_call", "put_sum", "put_mean", "smooth_put"):
+        for delta in (None, dp):
+            rc = _mc(lib, asian(pkg, g=g).to_c(), t=tp, x=xp, value=op, delta=delta)
+            assert rc != pkg._lib.DBSDE_EINVAL and (rc == pkg._lib.DBSDE_OK) == gpu, (g, rc, lib.dbsde_last_error(None))
+    if gpu:
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(dl).all())
+
+
+def test_python_checks_that_need_no_device():
+    pkg = load_pkg()
+    with pytest.raises(ValueError, match="Heston"):
+        pkg.ProblemSpec(kind="heston2", average=True).to_c()
+    with pytest.raises(ValueError, match=r"L must be \[3, 3\]"):
+        pkg.mc_value(asian(pkg), torch.zeros(1), torch.ones(1, 4), 1.0, 4, L=[[1.0, 0.0], [0.0, 1.0]])
