@@ -15,11 +15,14 @@ from .deepbsde import BlackScholesBarenblatt, u_exact
 from .fbsnn import FBSNN, PredictionGenerator
 from .problems import (AsianBasketCallOption, AsianBasketPutOption, AsianCallOption, AsianPutOption,
                        BasketCallOption, BasketPutOption, BSPDETestCase, CallOption, CallOption1D,
-                       HamiltonJacobiBellman, HestonFBSNN, HestonTwoFactorFBSNN, PutOption)
+                       GeometricAsianBasketCallOption, GeometricAsianBasketPutOption, GeometricAsianCallOption,
+                       GeometricAsianPutOption, HamiltonJacobiBellman, HestonFBSNN, HestonTwoFactorFBSNN, PutOption)
 from .solver import NativeSolver, ProblemSpec, exact, free_call_profile, hjb_mc, mc_value
 
 __all__ = ["FBSNN", "PredictionGenerator", "BlackScholesBarenblatt", "u_exact", "CallOption", "PutOption",
            "CallOption1D", "BasketCallOption", "BasketPutOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN", "HestonTwoFactorFBSNN",
            "AsianCallOption", "AsianPutOption", "AsianBasketCallOption", "AsianBasketPutOption",
+           "GeometricAsianCallOption", "GeometricAsianPutOption", "GeometricAsianBasketCallOption",
+           "GeometricAsianBasketPutOption",
            "NativeSolver", "ProblemSpec", "exact", "free_call_profile", "hjb_mc", "mc_value", "_lib"]

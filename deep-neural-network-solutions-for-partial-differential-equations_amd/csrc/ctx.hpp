@@ -46,6 +46,13 @@ inline const char* asian_refusal(const dbsde_problem& pr, int D) {
     return "the Asian problem takes the call and put payoffs only (not sumsq or log)";
   return nullptr;
 }
+// DBSDE_PROB_GEO_ASIAN (state [G, S_1..S_k]): asian_refusal's reasons, and the
+// assets must stay positive (the closed form is GBM's)
+inline const char* geo_asian_refusal(const dbsde_problem& pr, int D) {
+  if (const char* why = asian_refusal(pr, D)) return why;
+  if (pr.sig_b != 0.f) return "the geometric-average problem needs sig_b == 0 (log S needs positive assets)";
+  return nullptr;
+}
 
 struct Lin {
   long long w = -1, b = -1;
@@ -136,8 +143,9 @@ struct dbsde_ctx {
 
   // ---- network description
   int mode = 0, act = 0, K = 0, D = 0;
-  int nb = 0;                 // Brownian dimension (D; D/2 for Heston, kind 1; D - 1 for Asian, kind 4)
+  int nb = 0;                 // Brownian dimension (D; D/2 for Heston, kind 1; D - 1 for Asian, kinds 4 and 8)
   bool asian = false;         // DBSDE_PROB_ASIAN: state [A, S_1..S_k], A the running average (nb = D - 1)
+  bool geo = false;           // DBSDE_PROB_GEO_ASIAN: asian is set too, column 0 is the geometric average G
   int gcols = 0;              // state columns entering g and the terminal Z loss
   bool heston = false, u_clamp = false;
   bool heston2 = false;       // DBSDE_PROB_HESTON2: two Brownian motions per asset (nb = D)

@@ -101,6 +101,52 @@ __global__ void __launch_bounds__(256) exact_kernel(ExactArgs a) {
   if (a.delta) a.delta[i] = (float)delta;
 }
 
+// DBSDE_EXACT_GEO_ASIAN / _PUT: the option on the geometric average G_T = G exp((1/T)
+// int_t^T mean_i log S_i ds) of k correlated GBM assets (dS_i = mu S_i dt + sigma S_i
+// (L dW)_i), x = [G, S_1..S_k].  log G_T is normal with
+//   M = ln G + [tau mean_i ln S_i + (mu - sigma^2 cbar / 2) tau^2 / 2] / T,
+//   V = sigma^2 vbar tau^3 / (3 T^2),
+// cbar = mean_i (L L^T)_ii, vbar = 1^T L L^T 1 / k^2.  One thread per point; the put
+// is computed directly.  tau <= 0: the payoff and its 1 / 1/2 / 0 derivative in G.
+template <bool PUT>
+__global__ void __launch_bounds__(256) geo_asian_exact_kernel(ExactArgs a) {
+  const long long r = blockIdx.x * 256LL + threadIdx.x;
+  if (r >= a.R) return;
+  const double tau = a.T - (double)a.t[r];
+  const float* xr = a.x + r * a.D;
+  const int k = a.D - 1;
+  const double mu = a.p0, rr = a.p1, sig = a.p2, K = a.p3, cbar = a.p4, vbar = a.p5;
+  const double G = (double)xr[0];
+  double price, fwd;   // fwd: e^{-r tau} e^{M + V/2} N(+-d1) with the option's sign, the factor of every delta
+  if (tau > 0.0) {
+    double ml = 0.0;
+    for (int d = 1; d < a.D; ++d) ml += log((double)xr[d]);
+    ml /= (double)k;
+    const double M = log(G) + (tau * ml + (mu - 0.5 * sig * sig * cbar) * tau * tau * 0.5) / a.T;
+    const double V = sig * sig * vbar * tau * tau * tau / (3.0 * a.T * a.T);
+    const double sv = sqrt(V);
+    const double d2 = (M - log(K)) / sv, d1 = d2 + sv;
+    const double df = exp(-rr * tau), F = exp(M + 0.5 * V);
+    if constexpr (PUT) {
+      price = df * (K * ncdf(-d2) - F * ncdf(-d1));
+      fwd = -df * F * ncdf(-d1);
+    } else {
+      price = df * (F * ncdf(d1) - K * ncdf(d2));
+      fwd = df * F * ncdf(d1);
+    }
+  } else {
+    const double s = PUT ? K - G : G - K;
+    price = s > 0.0 ? s : 0.0;
+    fwd = (PUT ? -1.0 : 1.0) * (s > 0.0 ? 1.0 : (s == 0.0 ? 0.5 : 0.0)) * G;
+  }
+  a.price[r] = (float)price;
+  if (a.delta) {
+    float* dr = a.delta + r * a.D;
+    dr[0] = (float)(fwd / G);
+    for (int d = 1; d < a.D; ++d) dr[d] = tau > 0.0 ? (float)(fwd * tau / ((double)k * a.T * (double)xr[d])) : 0.f;
+  }
+}
+
 // --------------------------------------------------------------------------
 // DBSDE_EXACT_HESTON: the European call under the two-factor Heston model
 //   dS = r S dt + sqrt(v) S dW^S,  dv = kappa (theta - v) dt + sigma sqrt(v) dW^v,
@@ -316,8 +362,11 @@ extern "C" {
 
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* stream) {
-  if (kind < DBSDE_EXACT_BSB || kind > DBSDE_EXACT_HESTON_PUT || !t || !x || !params || !price || R < 1 || D < 1)
+  const bool geo = kind == DBSDE_EXACT_GEO_ASIAN || kind == DBSDE_EXACT_GEO_ASIAN_PUT;
+  if (kind < DBSDE_EXACT_BSB || (kind > DBSDE_EXACT_HESTON_PUT && !geo) || !t || !x || !params || !price || R < 1 ||
+      D < 1)
     return DBSDE_EINVAL;
+  if (geo && D < 2) return DBSDE_EINVAL;   // x = [G, S_1..S_k]
   // the kernels read and write whole floats: an address that is no multiple of
   // sizeof(float) (sizeof(double) for params) cannot be such a buffer, and is
   // refused here rather than handed to a launch
@@ -325,6 +374,29 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
   if (misaligned(t, sizeof(float)) || misaligned(x, sizeof(float)) || misaligned(price, sizeof(float)) ||
       misaligned(delta, sizeof(float)) || misaligned(params, sizeof(double)))
     return DBSDE_EINVAL;
+  if (geo) {   // params = {mu, r, sigma, K, cbar, vbar}; delta [R, D]
+    if ((R + 255) / 256 > 0x7fffffffLL) return DBSDE_EINVAL;
+    ExactArgs g{};
+    g.kind = kind;
+    g.D = D;
+    g.R = R;
+    g.T = T;
+    g.p0 = params[0];
+    g.p1 = params[1];
+    g.p2 = params[2];
+    g.p3 = params[3];
+    g.p4 = params[4];
+    g.p5 = params[5];
+    g.t = t;
+    g.x = x;
+    g.price = price;
+    g.delta = delta;
+    if (kind == DBSDE_EXACT_GEO_ASIAN_PUT)
+      geo_asian_exact_kernel<true><<<(unsigned)((R + 255) / 256), 256, 0, (hipStream_t)stream>>>(g);
+    else
+      geo_asian_exact_kernel<false><<<(unsigned)((R + 255) / 256), 256, 0, (hipStream_t)stream>>>(g);
+    return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
+  }
   // a put runs its call counterpart's shapes and parameters
   const bool put = kind >= DBSDE_EXACT_BS_PUT;
   if (put) kind -= DBSDE_EXACT_BS_PUT - DBSDE_EXACT_BS_CALL;

@@ -336,7 +336,7 @@ struct PdeArgs {
   dbsde_problem pr;
   int heston, D, nb, nd;   // heston: 0 DIAG, 1 HESTON, 2 HESTON2
   float rhob;              // HESTON2: fp32(sqrt(1 - (double)h_rho^2))
-  int asian;               // DBSDE_PROB_ASIAN: state [A, S_1..S_nb] (heston = 0)
+  int asian;               // 1 DBSDE_PROB_ASIAN: state [A, S_1..S_nb] (heston = 0); 2 DBSDE_PROB_GEO_ASIAN: [G, S]
   float T;                 // its averaging horizon
   const float* Lt;      // [nb][nb] L^T (dbsde_set_corr) or null
   const float* X;
@@ -357,7 +357,8 @@ struct PdeArgs {
 // asset i >= j the (S_i, v_i) entries of Sigma_i . (1, 1)^T times L[i][j];
 // two-factor Heston (nd = 1 + 2k) the 2k columns of its diffusion matrix;
 // arithmetic average (state [A, S_1..S_k], nd = 1 + k) DIAG's columns over the
-// S columns with A component 0
+// S columns with A component 0; geometric average (state [G, S_1..S_k]) the
+// same with G component 0
 __global__ void __launch_bounds__(256) pde_dirs_kernel(PdeArgs a) {
   const int ld = a.D + 1;
   const long long n = (long long)a.np * a.nd * ld;
@@ -435,15 +436,16 @@ __global__ void __launch_bounds__(256) pde_terms_kernel(PdeArgs a) {
     zz += zd * zd;
   }
   if (a.asian) {
-    // [A, S_1..S_k]: mu_a S_i on the S columns and mean S / T on A
+    // [A, S_1..S_k]: mu_a S_i on the S columns and mean S / T on A;
+    // [G, S_1..S_k]: G mean log S / T on G
     float ss = 0.f;
     drift = 0.f;
     for (int d = 1 + lane; d < D; d += 64) {
-      ss += x[d];
+      ss += a.asian == 2 ? logf(x[d]) : x[d];
       drift += a.pr.mu_a * x[d] * du[d];
     }
     ss = wave_sum(ss);
-    if (lane == 0) drift += ss / (float)a.nb / a.T * du[0];
+    if (lane == 0) drift += (a.asian == 2 ? x[0] : 1.f) * (ss / (float)a.nb / a.T) * du[0];
   }
   float tr = 0.f, atr = 0.f;
   for (int j = 1 + lane; j < a.nd; j += 64) {
@@ -696,7 +698,7 @@ int dbsde_pde_residual(dbsde_ctx* c, const float* params, int R, const float* t,
     pa.pr = c->cfg.problem;
     pa.heston = c->heston2 ? 2 : (c->heston ? 1 : 0);
     pa.rhob = c->rhob;
-    pa.asian = c->asian ? 1 : 0;
+    pa.asian = c->geo ? 2 : (c->asian ? 1 : 0);
     pa.T = c->cfg.T;
     pa.D = D;
     pa.nb = c->nb;

@@ -25,6 +25,12 @@
 // (sum_d I_d) / (k T) (T the averaging horizon, not tau_p), and mc_payoff runs
 // with one column.  Delta: dA_T/dA_p = 1 (the reducing threads sum dg/dA_T),
 // dA_T/dS_d = (sum_n (double)fp32(J_{d,n} dt_n)) / (k T) with DIAG's tangent J.
+// Geometric average (DBSDE_PROB_GEO_ASIAN, MC_GEO_ASIAN / MC_GEO_ASIAN_CORR):
+// state [G, S_1..S_k]; the same layout with I_d = sum_n (double)fp32(lg(S_{d,n})
+// dt_n) (geo_lg, sde.hpp) and G_T = G_p exp((sum_d I_d) / (k T)) in fp64 after the
+// end-of-path reduction -- the exponential form keeps "no reduction per step".
+// Delta: dG_T/dG_p = G_T / G_p, dG_T/dS_d = G_T (sum_n (double)fp32((J_{d,n} /
+// S_{d,n}) dt_n)) / (k T).
 //
 // Draws.  The normals of sample k, step n, Brownian coordinate d are
 // philox_normal4(seed, offset, k, n >> 2, d)[n & 3] -- the device-mode rollout's
@@ -101,10 +107,15 @@ constexpr int MC_LPACK = MC_NBMAX * (MC_NBMAX + 1) / 2;
 constexpr int MC_HCMAX = 511;      // correlated Heston: dbsde_set_corr's limit for Heston contexts
 constexpr int MC_WS_MB = 1024;     // correlated Heston: default workspace bound (DBSDE_MC_WS_MB)
 constexpr int MC_ZMAX = 2048;       // correlated: floats of the Z (and C) tile, nd x (4 S padded to 16) <= 2048
-enum { MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2, MC_HESTON2 = 3, MC_ASIAN = 4, MC_ASIAN_CORR = 5 };
-// the kinds whose increments go through the L . Z product, and the arithmetic-average kinds
-constexpr bool mc_corr(int kind) { return kind == MC_CORR || kind == MC_ASIAN_CORR; }
-constexpr bool mc_asian(int kind) { return kind == MC_ASIAN || kind == MC_ASIAN_CORR; }
+enum {
+  MC_DIAG = 0, MC_CORR = 1, MC_HESTON = 2, MC_HESTON2 = 3, MC_ASIAN = 4, MC_ASIAN_CORR = 5,
+  MC_GEO_ASIAN = 6, MC_GEO_ASIAN_CORR = 7
+};
+// the kinds whose increments go through the L . Z product, the running-average kinds (state
+// [A or G, S_1..S_k], a time integral per asset), and the geometric ones among those
+constexpr bool mc_geo(int kind) { return kind == MC_GEO_ASIAN || kind == MC_GEO_ASIAN_CORR; }
+constexpr bool mc_corr(int kind) { return kind == MC_CORR || kind == MC_ASIAN_CORR || kind == MC_GEO_ASIAN_CORR; }
+constexpr bool mc_asian(int kind) { return kind == MC_ASIAN || kind == MC_ASIAN_CORR || mc_geo(kind); }
 
 typedef float mcf4 __attribute__((ext_vector_type(4)));
 
@@ -274,8 +285,13 @@ __device__ __forceinline__ void mc_path(const McArgs& a, uint32_t k, int d, int 
           heston_step(heston_coef(a.mu, a.kappa, a.theta, a.hsig, a.rho, X[i], V[i]), dt, w, X[i], V[i], sa, sb);
         } else {
           if constexpr (mc_asian(KIND)) {   // the left-point rule: S (and J) at the start of the step
-            AI[i] += (double)rn_mul(X[i], dt);
-            if constexpr (DELTA) AJ[i] += (double)rn_mul(V[i], dt);
+            if constexpr (mc_geo(KIND)) {
+              AI[i] += (double)rn_mul(geo_lg(X[i]), dt);
+              if constexpr (DELTA) AJ[i] += (double)rn_mul(V[i] / X[i], dt);
+            } else {
+              AI[i] += (double)rn_mul(X[i], dt);
+              if constexpr (DELTA) AJ[i] += (double)rn_mul(V[i], dt);
+            }
           }
           diag_step(a.mu, a.sig_a, a.sig_b, dt, w, X[i]);
           if constexpr (DELTA) diag_tangent_step(a.mu, a.sig_a, dt, w, V[i]);
@@ -314,6 +330,7 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
   // arithmetic average: the state columns are [A, S_1..S_nd], a sample's payoff terms are the
   // time integrals I_d of its assets, and A_T = A_p + (sum_d I_d) / (nd T)
   constexpr bool ASIAN = mc_asian(KIND);
+  constexpr bool GEO = mc_geo(KIND);   // [G, S_1..S_nd]: G_T = G_p exp((sum_d I_d) / (nd T)), I_d over lg(S_d)
   constexpr int XO = ASIAN ? 1 : 0;
   const double akt = (double)nd * (double)a.T;
   float sq[MC_PT];
@@ -372,15 +389,21 @@ __global__ void __launch_bounds__(MC_THREADS) mc_kernel(McArgs a) {
       const double* fr = fred + ri * MC_THREADS + rs * RW;
       double sum = 0.0;
       for (int e = 0; e < RW; ++e) sum += fr[e];
-      if constexpr (ASIAN) sum = (double)a.x[(size_t)(p0 + ri < a.P ? p0 + ri : a.P - 1) * a.D] + sum / akt;   // A_T
+      double gfac = 1.0;   // GEO: G_T / G_p = dG_T / dG_p
+      if constexpr (GEO) {
+        gfac = exp(sum / akt);
+        sum = (double)a.x[(size_t)(p0 + ri < a.P ? p0 + ri : a.P - 1) * a.D] * gfac;   // G_T
+      } else if constexpr (ASIAN) {
+        sum = (double)a.x[(size_t)(p0 + ri < a.P ? p0 + ri : a.P - 1) * a.D] + sum / akt;   // A_T
+      }
       double g, gp;
       mc_payoff(a.g_kind, sum, cols, K, alpha, g, gp);
       if (kb + rs < k1) {
         gs += g;
         g2 += g * g;
-        if constexpr (ASIAN && DELTA) gps += gp;
+        if constexpr (ASIAN && DELTA) gps += GEO ? gp * gfac : gp;
       }
-      gpl[tid] = (float)gp;
+      gpl[tid] = GEO ? (float)(gp * sum) : (float)gp;   // GEO: dg/dG_T . G_T, the factor of every dS_d
     }
     __syncthreads();
     if constexpr (DELTA) {
@@ -509,7 +532,7 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (mc > (1LL << 32)) return bad("mc must be <= 2^32 (the sample index is a 32-bit counter word)");
   if (D > MC_DMAX) return bad("D must be <= 4096");
   if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2 &&
-      prob->kind != DBSDE_PROB_HESTON_CORR && prob->kind != DBSDE_PROB_ASIAN)
+      prob->kind != DBSDE_PROB_HESTON_CORR && prob->kind != DBSDE_PROB_ASIAN && prob->kind != DBSDE_PROB_GEO_ASIAN)
     return bad("unknown problem kind");
   if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_PUT) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
@@ -526,9 +549,11 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (hcorr && D / 2 > MC_HCMAX) return bad("correlated Heston needs k = D / 2 <= 511");
   if (hcorr && (n_steps + 3) / 4 > 65535) return bad("correlated Heston needs n_steps <= 262140");
   // arithmetic average: state [A, S_1..S_k], the DIAG process on the k = D - 1 assets, payoff on A
-  const bool asian = prob->kind == DBSDE_PROB_ASIAN;
+  // geometric average: state [G, S_1..S_k], the same layout (asian is set too)
+  const bool geo = prob->kind == DBSDE_PROB_GEO_ASIAN;
+  const bool asian = prob->kind == DBSDE_PROB_ASIAN || geo;
   if (asian) {
-    if (const char* why = asian_refusal(*prob, D)) return bad(why);
+    if (const char* why = geo ? geo_asian_refusal(*prob, D) : asian_refusal(*prob, D)) return bad(why);
     if (L && D - 1 > MC_NBMAX) return bad("L needs D - 1 <= 128 assets");
   }
   if (!hcorr && !asian && L && D > MC_NBMAX) return bad("L needs D <= 128");
@@ -621,6 +646,14 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
     mc_kernel<MC_HESTON2, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (heston)
     mc_kernel<MC_HESTON, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (geo && L && delta)
+    mc_kernel<MC_GEO_ASIAN_CORR, true><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (geo && L)
+    mc_kernel<MC_GEO_ASIAN_CORR, false><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (geo && delta)
+    mc_kernel<MC_GEO_ASIAN, true><<<grid, MC_THREADS, 0, st>>>(a);
+  else if (geo)
+    mc_kernel<MC_GEO_ASIAN, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (asian && L && delta)
     mc_kernel<MC_ASIAN_CORR, true><<<grid, MC_THREADS, 0, st>>>(a);
   else if (asian && L)

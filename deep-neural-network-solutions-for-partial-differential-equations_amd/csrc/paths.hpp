@@ -1011,6 +1011,8 @@ constexpr int AA_THREADS = 256;   // 16 paths per workgroup
 constexpr int AA_TERMS = 8;       // loads of one lane sum in flight
 // asian_lane_sum (sde.hpp): the same terms added in the same order, their loads
 // issued AA_TERMS at a time ahead of the adds
+// GEO (geo_lane_sum): the terms are lg(S_i), taken after the loads
+template <bool GEO>
 __device__ __forceinline__ float asian_lane_sum_ahead(const float* S, int k, int lane) {
   float p = 0.f;
   for (int i0 = lane; i0 < k; i0 += AA_TERMS * ASIAN_LANES) {
@@ -1019,10 +1021,13 @@ __device__ __forceinline__ float asian_lane_sum_ahead(const float* S, int k, int
     for (int j = 0; j < AA_TERMS; ++j) v[j] = i0 + j * ASIAN_LANES < k ? S[i0 + j * ASIAN_LANES] : 0.f;
 #pragma unroll
     for (int j = 0; j < AA_TERMS; ++j)
-      if (i0 + j * ASIAN_LANES < k) p = rn_add(p, v[j]);
+      if (i0 + j * ASIAN_LANES < k) p = rn_add(p, GEO ? geo_lg(v[j]) : v[j]);
   }
   return p;
 }
+// GEO (DBSDE_PROB_GEO_ASIAN): the carried value is a = log G (a_0 = lg(G_0)), the
+// row terms are lg(S_i), row 0 stores G_0 as given and row n >= 1 exp(a_n)
+template <bool GEO>
 __global__ void __launch_bounds__(AA_THREADS) rollout_asian_avg_kernel(RolloutArgs p) {
   const long long gid = (long long)blockIdx.x * AA_THREADS + threadIdx.x;
   const bool ok = gid / ASIAN_LANES < p.M;   // (a 16-lane group is one path: its lanes agree)
@@ -1030,13 +1035,15 @@ __global__ void __launch_bounds__(AA_THREADS) rollout_asian_avg_kernel(RolloutAr
   const int k = p.nb, N1 = p.N + 1;
   const float* xr = p.xin + (size_t)m * N1 * p.ldx;
   float A = ok ? p.Xi[(size_t)(p.xi_rows == 1 ? 0 : m) * p.D] : 0.f;
+  const float G0 = A;
+  if constexpr (GEO) A = geo_lg(A);
   for (int n0 = 0; n0 <= p.N; n0 += AA_ROWS) {
     float s[AA_ROWS], dt[AA_ROWS];
 #pragma unroll
     for (int j = 0; j < AA_ROWS; ++j) {
       const int n = n0 + j;
       const bool row = ok && n < p.N;
-      s[j] = row ? asian_lane_sum_ahead(xr + (size_t)n * p.ldx + 2, k, l) : 0.f;
+      s[j] = row ? asian_lane_sum_ahead<GEO>(xr + (size_t)n * p.ldx + 2, k, l) : 0.f;
       dt[j] = row ? rn_sub(xr[(size_t)(n + 1) * p.ldx], xr[(size_t)n * p.ldx]) : 0.f;
     }
 #pragma unroll
@@ -1048,7 +1055,7 @@ __global__ void __launch_bounds__(AA_THREADS) rollout_asian_avg_kernel(RolloutAr
     for (int j = 0; j < AA_ROWS; ++j) {
       const int n = n0 + j;
       if (!ok || n > p.N) break;
-      if (l == 0) p.xin[((size_t)m * N1 + n) * p.ldx + 1] = A;
+      if (l == 0) p.xin[((size_t)m * N1 + n) * p.ldx + 1] = GEO ? (n == 0 ? G0 : geo_exp(A)) : A;
       if (n < p.N) asian_step(asian_mean(s[j], k), dt[j], p.T, A);
     }
   }

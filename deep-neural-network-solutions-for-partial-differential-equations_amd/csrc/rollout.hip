@@ -9,6 +9,8 @@
 // Two-factor Heston (DBSDE_PROB_HESTON2): rollout_heston2_kernel for everything.
 // Arithmetic average (DBSDE_PROB_ASIAN): rollout_asian_chain_kernel (behind the
 // increment GEMM when a factor is set), then rollout_asian_avg_kernel.
+// Geometric average (DBSDE_PROB_GEO_ASIAN): the same two launches, the second
+// its geometric instance.
 #include <hip/hip_runtime.h>
 
 // a prefetched rollout runs on the next chunked step's second stream
@@ -189,8 +191,12 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
     }
     // reads the k S columns and t of every row, writes the A column
     const int groups = ra.M * ASIAN_LANES;
-    RUN(c, s, "asian_avg", 3.0 * steps * k, 4.0 * steps * (k + 2.0),
-        rollout_asian_avg_kernel<<<(groups + AA_THREADS - 1) / AA_THREADS, AA_THREADS, 0, s>>>(ra));
+    if (c->geo)
+      RUN(c, s, "geo_asian_avg", 3.0 * steps * k, 4.0 * steps * (k + 2.0),
+          rollout_asian_avg_kernel<true><<<(groups + AA_THREADS - 1) / AA_THREADS, AA_THREADS, 0, s>>>(ra));
+    else
+      RUN(c, s, "asian_avg", 3.0 * steps * k, 4.0 * steps * (k + 2.0),
+          rollout_asian_avg_kernel<false><<<(groups + AA_THREADS - 1) / AA_THREADS, AA_THREADS, 0, s>>>(ra));
   } else if (c->heston2) {
     // two-factor Heston (never with a factor: dbsde_set_corr refuses it): one
     // kernel for device- and parity-mode batches, in-step and prefetched, and

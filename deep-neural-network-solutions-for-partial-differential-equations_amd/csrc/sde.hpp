@@ -124,4 +124,31 @@ DBSDE_HD float asian_mean(float sum, int k) { return sum / (float)k; }
 // A_{n+1} from A_n, the row mean m_n of S_n and dt_n
 DBSDE_HD void asian_step(float m, float dt, float T, float& A) { A = rn_add(A, rn_mul(m, dt) / T); }
 
+// Geometric-average problems (DBSDE_PROB_GEO_ASIAN): state [G, S_1..S_k], G
+// the running geometric average exp((1/T) int mean_i log S_i dt).  The
+// arithmetic machinery above runs on lg(S_i) and carries a = log G; the stored
+// column is exp(a):
+//   lg_i = (float)log((double)max(S_i, FLT_MIN))     (fp64 log, rounded to fp32 once)
+//   m    = (sum_i lg_i) / (float)k                   (asian_lane_sum / asian_row_sum's order on lg)
+//   a'   = a + (m dt) / T                            (asian_step on a),  a_0 = lg(G_0)
+//   G_n  = (float)exp((double)a_n), n >= 1;  row 0 holds G_0 as given
+// so G_N = G_0 exp((1/T) sum_n m_n dt_n).
+DBSDE_HD float geo_lg(float S) { return (float)log((double)fmaxf(S, 1.17549435e-38f)); }   // FLT_MIN
+DBSDE_HD float geo_exp(float a) { return (float)exp((double)a); }
+DBSDE_HD float geo_lane_sum(const float* S, int k, int lane) {
+  float p = 0.f;
+  for (int i = lane; i < k; i += ASIAN_LANES) p = rn_add(p, geo_lg(S[i]));
+  return p;
+}
+DBSDE_HD float geo_row_sum(const float* S, int k) {
+  float p[ASIAN_LANES];
+  for (int l = 0; l < ASIAN_LANES; ++l) p[l] = geo_lane_sum(S, k, l);
+  for (int o = 1; o < ASIAN_LANES; o <<= 1) {
+    float q[ASIAN_LANES];
+    for (int l = 0; l < ASIAN_LANES; ++l) q[l] = rn_add(p[l], p[l ^ o]);
+    for (int l = 0; l < ASIAN_LANES; ++l) p[l] = q[l];
+  }
+  return p[0];
+}
+
 }  // namespace dbsde

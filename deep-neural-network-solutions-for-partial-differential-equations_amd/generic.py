@@ -43,9 +43,11 @@ def spec_functions(spec, strike=None, T=None):
     """The coefficients a DIAG ProblemSpec declares (include/dbsde.h), as
     torch functions of the reference methods' signatures.  An average=True
     spec (state [A, S_1..S_k], DBSDE_PROB_ASIAN) has the A row mean S / T in mu
-    (T is then required) and a zero A row in sigma [R, 1 + k, k]."""
+    (T is then required) and a zero A row in sigma [R, 1 + k, k]; an
+    average="geometric" spec (state [G, S_1..S_k]) the G row G mean log S / T."""
     K = spec.strike if strike is None else strike
     average = bool(getattr(spec, "average", False))
+    geometric = average and spec.average_kind() == "geometric"
     if average and T is None:
         raise ValueError("spec_functions needs T for an average=True spec (the A drift is mean S / T)")
 
@@ -55,6 +57,8 @@ def spec_functions(spec, strike=None, T=None):
     def mu(t, X, Y=None, Z=None):
         if average:
             S = X[:, 1:]
+            if geometric:
+                return torch.cat([X[:, :1] * torch.mean(torch.log(S), dim=1, keepdim=True) / T, spec.mu_a * S], dim=1)
             return torch.cat([torch.mean(S, dim=1, keepdim=True) / T, spec.mu_a * S], dim=1)
         return spec.mu_a * X
 

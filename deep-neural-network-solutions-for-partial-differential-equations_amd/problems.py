@@ -17,6 +17,9 @@ methods (generic.py) instead of silently training the parent's problem.
   AsianCallOption / AsianPutOption, AsianBasketCallOption / AsianBasketPutOption
                         (no reference counterpart)      arithmetic-average options: the running
                                                         average as one more state coordinate
+  GeometricAsianCallOption / GeometricAsianPutOption, GeometricAsianBasketCallOption /
+  GeometricAsianBasketPutOption
+                        (no reference counterpart)      geometric-average options, with a closed form
   BlackScholesBarenblatt: see deepbsde.py (DeepBSDE.py:326-341 surface)
 """
 from __future__ import annotations
@@ -433,8 +436,9 @@ class _AsianState:
     is prepended; rows of D + 1 columns are taken as [A, S] as given).  predict
     returns X [M, N+1, D + 1] with A in column 0; net_u, theta, pde_residual and
     mc_value take points [A, S_1..S_D] (mc_value also [S_1..S_D] with A = 0).
-    Limits: the average is arithmetic with a fixed strike (no geometric or
-    floating-strike average), there is no closed form, the assets are diagonal
+    Limits: the average is arithmetic with a fixed strike (no floating-strike
+    average; the geometric average is the Geometric* classes), it has no closed
+    form (the geometric price is its lower bound), the assets are diagonal
     processes (no average over Heston states), and a subclass overriding a
     coefficient method with other coefficients is refused (NotImplementedError)
     instead of running on the generic path."""
@@ -532,6 +536,94 @@ class AsianBasketPutOption(AsianBasketCallOption):
     option_type = "put"
 
 
+class _GeoAsianState(_AsianState):
+    """The geometric-average Asian option on D assets (no reference counterpart;
+    problem kind DBSDE_PROB_GEO_ASIAN, ProblemSpec(average="geometric")).
+
+    _AsianState's surface with the state [G, S_1..S_D], G the running geometric
+    average exp((1/T) int_0^t mean_i log S_i ds): G_0 = 1 (prepended to Xi; rows
+    of D + 1 columns are [G, S] as given), dG = G (mean_i log S_i / T) dt, every
+    S_i the GBM dS = 0.05 S dt + 0.20 S dW_i, and u(t, G, S) solves
+
+      u_t + G (mean log S / T) u_G + sum_i 0.05 S_i u_{S_i} + 1/2 tr(sigma sigma^T D^2_S u) - 0.05 u = 0,
+      u(T, .) = g(G).
+
+    G_T is log-normal, so the unsmoothed option has a closed form at any D and
+    with a Cholesky factor between the assets: closed_form().  It is the
+    continuous-time value; the training grid's scheme (the left-point rule on
+    log S) differs from it by O(dt).  Limits: fixed strike, sig_b = 0 (GBM
+    assets), no Heston states; mc_value with a factor keeps D <= 128."""
+
+    def _full_state(self, Xi):
+        """[S_1..S_D] -> [1, S_1..S_D]; rows of D + 1 columns are [G, S] already.
+        Values held on the host are checked: G and every S must be positive."""
+        k = self.n_assets
+        host = not (isinstance(Xi, torch.Tensor) and Xi.device.type != "cpu")
+        x = torch.as_tensor(np.asarray(Xi) if not isinstance(Xi, torch.Tensor) else Xi, dtype=torch.float32)
+        x = x.reshape(-1, x.shape[-1]) if x.dim() > 1 else x.reshape(1, -1)
+        if host and not bool((x > 0).all()):
+            raise ValueError("the geometric average needs G > 0 and every S_i > 0")
+        x = x.to(self.device)
+        if x.shape[1] == k + 1:
+            return x.contiguous()
+        if x.shape[1] != k:
+            raise ValueError(f"Xi has {x.shape[1]} columns; expected the {k} asset prices (or [G, S]: {k + 1})")
+        return torch.cat([torch.ones_like(x[:, :1]), x], 1).contiguous()
+
+    def problem_spec(self):
+        return dataclasses.replace(super().problem_spec(), average="geometric")
+
+    def mu_tf(self, t, X, Y=None, Z=None):
+        S = X[:, 1:]
+        return torch.cat([X[:, :1] * torch.mean(torch.log(S), dim=1, keepdim=True) / self.T, 0.05 * S], dim=1)
+
+    def closed_form(self, G, S, t):
+        """The continuous-time price of this object's option at the points
+        (G [R], S [R, D], t [R]): (price [R, 1], delta [R, D + 1] = [d/dG,
+        d/dS_1..d/dS_D]) as float32 tensors on the device, through
+        exact("geo_asian", ...) -- "geo_asian_put" for option_type "put" -- with
+        mu = r = 0.05, sigma = 0.20, this object's strike and T, and cbar, vbar
+        of this object's own Cholesky factor.  The unsmoothed payoff
+        ('discontinuous') only."""
+        if self.payoff_type != "discontinuous":
+            raise ValueError("closed_form prices the unsmoothed payoff ('discontinuous') only")
+        k = self.n_assets
+        G = torch.as_tensor(np.asarray(G) if not isinstance(G, torch.Tensor) else G, dtype=torch.float32).reshape(-1, 1)
+        S = torch.as_tensor(np.asarray(S) if not isinstance(S, torch.Tensor) else S, dtype=torch.float32).reshape(-1, k)
+        t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t, dtype=torch.float32).reshape(-1)
+        if not (G.shape[0] == S.shape[0] == t.numel()):
+            raise ValueError("G, S and t must hold the same number of points")
+        X = self._full_state(torch.cat([G.to(S.device), S], dim=1))
+        L = np.eye(k) if self._L is None else np.tril(np.asarray(self._L, dtype=np.float64))
+        C = L @ L.T
+        cbar, vbar = float(np.trace(C)) / k, float(C.sum()) / (k * k)
+        kind = "geo_asian_put" if self.option_type == "put" else "geo_asian"
+        return _exact(kind, t.to(self.device), X, self.T, (0.05, 0.05, 0.20, self.strike, cbar, vbar))
+
+
+class GeometricAsianCallOption(_GeoAsianState, FBSNN):
+    """The geometric-average call max(G_T - K, 0), K = 1 by default, on
+    CallOption's surface (its train(), schedule and gradient clipping)."""
+
+
+class GeometricAsianPutOption(GeometricAsianCallOption):
+    """GeometricAsianCallOption's problem with the put payoff max(K - G_T, 0)."""
+
+    option_type = "put"
+
+
+class GeometricAsianBasketCallOption(_GeoAsianState, _WithCorrTrain, FBSNN):
+    """The geometric-average call on a basket, on BasketCallOption's surface:
+    its train() (the N**(1/5) schedule, time_logs) and correlated increments."""
+
+
+class GeometricAsianBasketPutOption(GeometricAsianBasketCallOption):
+    """GeometricAsianBasketCallOption's problem with the put payoff max(K - G_T, 0)."""
+
+    option_type = "put"
+
+
 __all__ = ["CallOption", "PutOption", "CallOption1D", "BasketCallOption", "BasketPutOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN", "HestonTwoFactorFBSNN", "AsianCallOption", "AsianPutOption", "AsianBasketCallOption",
-           "AsianBasketPutOption"]
+           "AsianBasketPutOption", "GeometricAsianCallOption", "GeometricAsianPutOption",
+           "GeometricAsianBasketCallOption", "GeometricAsianBasketPutOption"]

@@ -29,7 +29,10 @@ class ProblemSpec:
     average (kind "diag" only): the arithmetic-average (Asian) problem
     DBSDE_PROB_ASIAN -- state [A, S_1..S_k], every S_i the diag process, A the
     running average of mean_i S_i (A' = A + mean S dt / T), nb = k; the payoff
-    is on A alone (g_cols = 1, a call or put g, phi_c = 0)."""
+    is on A alone (g_cols = 1, a call or put g, phi_c = 0).  average is False,
+    True or "arithmetic" (the same), or "geometric": DBSDE_PROB_GEO_ASIAN --
+    state [G, S_1..S_k], G the running geometric average
+    exp((1/T) int mean_i log S_i dt), G_0 = 1, sig_b = 0; the payoff is on G."""
 
     mu_a: float = 0.0
     sig_a: float = 0.0
@@ -50,15 +53,25 @@ class ProblemSpec:
     rho: float = 0.0
     average: bool = False
 
+    def average_kind(self):
+        """None, "arithmetic" or "geometric"."""
+        if isinstance(self.average, str):
+            if self.average not in ("arithmetic", "geometric"):
+                raise ValueError(f"unknown average {self.average!r}: False, True, 'arithmetic' or 'geometric'")
+            return self.average
+        return "arithmetic" if self.average else None
+
     def to_c(self):
         if self.g not in _lib.G_KINDS:
             raise ValueError(f"unknown terminal condition {self.g!r}")
         if self.kind not in _lib.PROBLEM_KINDS:
             raise ValueError(f"unknown problem kind {self.kind!r}")
-        if self.average and self.kind != "diag":
+        average = self.average_kind()
+        if average and self.kind != "diag":
             raise ValueError("average=True (the Asian problem) needs kind 'diag': an average over Heston states is "
                              "not supported")
-        kind = _lib.PROB_ASIAN if self.average else _lib.PROBLEM_KINDS[self.kind]
+        kind = {None: _lib.PROBLEM_KINDS[self.kind], "arithmetic": _lib.PROB_ASIAN,
+                "geometric": _lib.PROB_GEO_ASIAN}[average]
         return _lib.Problem(kind, self.mu_a, self.sig_a, self.sig_b, self.phi_r,
                             self.phi_c, self.phi_zz, _lib.G_KINDS[self.g], self.strike, int(self.q3),
                             int(self.g_cols), self.g_alpha, int(self.u_clamp), self.kappa, self.theta,
@@ -420,7 +433,11 @@ def exact(kind, t, X, T, params):
     = (S, v), params = (r, K, kappa, theta, sigma, rho), delta [R, 1] = dprice/dS.
     "bs_put", "basket_avg_put", "basket_mean_put" and "heston_put" are the
     European puts with the parameters and shapes of their call counterparts,
-    computed directly (not as the call minus parity)."""
+    computed directly (not as the call minus parity).  "geo_asian" /
+    "geo_asian_put": the options on the geometric average in continuous time,
+    X [R, 1 + k] = [G, S_1..S_k], T the averaging horizon, params = (mu, r,
+    sigma, K, cbar, vbar) (cbar = mean diag(L L^T), vbar = 1^T L L^T 1 / k^2;
+    1 and 1 / k without a factor), price [R, 1], delta [R, 1 + k]."""
     lib = _lib.load()
     if kind not in _lib.EXACT_KINDS:
         raise ValueError(f"unknown exact solution {kind!r}")
@@ -430,15 +447,20 @@ def exact(kind, t, X, T, params):
     if t.numel() != R or X.device.type != "cuda" or t.device != X.device:
         raise ValueError("t [R] and X [R, D] must be float32 tensors on the same HIP device")
     heston = kind in ("heston", "heston_put")
+    geo = kind in ("geo_asian", "geo_asian_put")
+    if geo and D < 2:
+        raise ValueError(f"{kind!r} takes X [R, 1 + k] = [G, S_1..S_k]")
     ncol = D if kind in ("bs_call", "bs_put") else 1
     price = torch.empty((R, ncol), device=X.device)
-    delta = None if kind == "bsb" else torch.empty((R, ncol), device=X.device)
+    delta = None if kind == "bsb" else torch.empty((R, D if geo else ncol), device=X.device)
     import numpy as np
     p = np.zeros(6, dtype=np.float64)
-    if len(params) > (6 if heston else 3):
+    if len(params) > (6 if heston or geo else 3):
         raise ValueError(f"too many parameters for {kind!r}")
     if heston and len(params) != 6:
         raise ValueError(f"{kind!r} takes params = (r, K, kappa, theta, sigma, rho)")
+    if geo and len(params) != 6:
+        raise ValueError(f"{kind!r} takes params = (mu, r, sigma, K, cbar, vbar)")
     p[:len(params)] = params
     s = torch.cuda.current_stream(X.device).cuda_stream
     _lib.check(lib.dbsde_exact(_lib.EXACT_KINDS[kind], _ptr(t), _ptr(X), R, D, float(T),
@@ -473,7 +495,8 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
     Brownian motions for kind "heston" (the process of a Heston solver with
     set_corr; sent as DBSDE_PROB_HESTON_CORR); "heston2" takes none; an
     average=True spec (X [P, 1 + k] = [A, S_1..S_k]) takes [k, k], k <= 128,
-    and its delta is [dA, dS_1..dS_k].  Returns
+    and its delta is [dA, dS_1..dS_k] (average="geometric": X = [G, S_1..S_k],
+    delta [dG, dS_1..dS_k]; its continuous-time value is exact("geo_asian")).  Returns
     (value [P, 1], stderr [P, 1], delta [P, D] or None); delta is the pathwise
     estimator (diag only)."""
     if spec.phi_zz != 0:

@@ -91,6 +91,12 @@ extern "C" {
                               /* arithmetic-average (Asian) option on k DIAG assets: state
                                  [A, S_1..S_k], A the running average of mean_i S_i, one
                                  Brownian motion per asset (nb = D - 1)                */
+/* kind 8 (5, 6 and 7 are unknown kinds: tests/test_abi_asian.py), an expression for the
+   same reason; tests/test_abi_geo_asian.py holds the compiled value to 8 */
+#define DBSDE_PROB_GEO_ASIAN (DBSDE_PROB_ASIAN + 4)
+                              /* geometric-average Asian option on k GBM assets: state
+                                 [G, S_1..S_k], G = exp((1/T) int mean_i log S_i dt) the
+                                 running geometric average (nb = D - 1)                */
 
 /*
  * Problem coefficients (one FBSNN subclass = one filled struct):
@@ -142,6 +148,22 @@ extern "C" {
  *     DBSDE_EINVAL); phi_c must be 0 (X.Z would include A u_A); q3 is ignored.
  *     dbsde_pde_residual takes nd = 1 + k directions (A component 0) and the
  *     drift above; dbsde_mc_value simulates the same process (below).
+ *   kind GEO_ASIAN, the same struct: state [G, S_1..S_k], D = k + 1 >= 2, nb = k, ASIAN's
+ *     S columns, increments, factor (dbsde_set_corr, L [k, k]) and refusals, and sig_b
+ *     must be 0 (DBSDE_EINVAL: the assets must stay positive, and the closed form
+ *     DBSDE_EXACT_GEO_ASIAN is GBM's).  G has no diffusion, dG = G (mean_i log S_i / T) dt,
+ *     G_0 = 1 for an option written at t = 0.  The scheme carries a = log G through
+ *     ASIAN's averaging on lg(S), every operation rounded to fp32 on its own unless cast:
+ *       lg_i = (float)log((double)fmaxf(S_i, FLT_MIN))   (one definition, host and device)
+ *       p_l, butterfly, m = sum / (float)k               ASIAN's order, on lg
+ *       a'   = a + (m dt) / T                            a_0 = lg(G_0) (exactly 0 for G_0 = 1)
+ *       row 0 stores G_0 as given; row n >= 1 stores G_n = (float)exp((double)a_n)
+ *     so G_N = G_0 exp((1/T) sum_n m_n dt_n).  sigma dW: G: exactly 0, S_i: (sig_a S_i) dW_i.
+ *     The PDE is
+ *       u_t + G (mean log S / T) u_G + sum_i mu_a S_i u_{S_i} + 1/2 tr(sigma sigma^T D^2_S u) - phi = 0,
+ *       u(T, .) = g(G),
+ *     g_cols = 1.  dbsde_pde_residual takes ASIAN's directions (G component 0) and this
+ *     drift (logf of the S columns); dbsde_mc_value simulates the same process (below).
  *   phi      =phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
  *   g        = g_kind over the first g_cols state columns (0 = all), strike,
  *              g_alpha (DBSDE_G_SMOOTH_CALL / _PUT); the terminal |Z - grad g|^2 term
@@ -217,7 +239,7 @@ int dbsde_param_used_mask(const dbsde_ctx* ctx, unsigned char* mask, long long n
 int dbsde_matrix_form(const dbsde_ctx* ctx);
 
 /* Brownian dimension nb of a batch's W [M, N+1, nb]: D (DIAG, HESTON2), D/2 for HESTON,
-   D - 1 for ASIAN */
+   D - 1 for ASIAN and GEO_ASIAN */
 int dbsde_brownian_dim(const dbsde_ctx* ctx);
 
 /*
@@ -500,11 +522,26 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
  *                            accuracy); Heston: K exp(-r tau) (1 - P2) - S (1 - P1),
  *                            delta -(1 - P1), with 1 - P_j = 1/2 - I_j / pi from the
  *                            call's quadrature sums I_j (same panels, same U).
- * t [R], x [R, D] device fp32; price and delta (nullable) [R * ncol],
- * ncol = D for BS_CALL / BS_PUT, 1 otherwise.  At t >= T the payoff and its
+ *   DBSDE_EXACT_GEO_ASIAN, DBSDE_EXACT_GEO_ASIAN_PUT
+ *                            the call / put on the geometric average of kind
+ *                            DBSDE_PROB_GEO_ASIAN in continuous time: x [R, D] = [G,
+ *                            S_1..S_k], D >= 2, T the averaging horizon, params = {mu, r,
+ *                            sigma, K, cbar, vbar}, cbar = mean_i (L L^T)_ii and vbar =
+ *                            1^T L L^T 1 / k^2 of the factor between the assets (1 and
+ *                            1 / k without one).  With tau = T - t,
+ *                              M = ln G + [tau mean_i ln S_i + (mu - sigma^2 cbar / 2) tau^2 / 2] / T
+ *                              V = sigma^2 vbar tau^3 / (3 T^2)
+ *                              d2 = (M - ln K) / sqrt(V),  d1 = d2 + sqrt(V)
+ *                              call = e^{-r tau} [e^{M + V/2} N(d1) - K N(d2)]
+ *                              put  = e^{-r tau} [K N(-d2) - e^{M + V/2} N(-d1)]  (directly)
+ *                            delta [R, D]: d/dG = +-e^{-r tau} e^{M + V/2} N(+-d1) / G,
+ *                            d/dS_i = that G tau / (k T S_i).  Needs sigma, K, G, S > 0.
+ *                            (Kind 9 is not a closed form: DBSDE_EINVAL.)
+ * t [R], x [R, D] device fp32; price [R * ncol] and delta (nullable),
+ * ncol = D for BS_CALL / BS_PUT, 1 otherwise (GEO_ASIAN: price [R], delta [R, D]).  At t >= T the payoff and its
  * 0 / 1/2 / 1 (put: 0 / -1/2 / -1) delta are returned, as the references do.
  * Computed in fp64.  DBSDE_EINVAL before any HIP call: an unknown kind; NULL t /
- * x / params / price; R or D < 1; a Heston kind with D != 2; t, x, price or
+ * x / params / price; R or D < 1; a Heston kind with D != 2; a GEO_ASIAN kind with D < 2; t, x, price or
  * delta not aligned to sizeof(float), params not to sizeof(double) (such an
  * address cannot be the buffer the kernels read and write).
  */
@@ -517,6 +554,8 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
 #define DBSDE_EXACT_BASKET_AVG_PUT 6
 #define DBSDE_EXACT_BASKET_MEAN_PUT 7
 #define DBSDE_EXACT_HESTON_PUT 8
+#define DBSDE_EXACT_GEO_ASIAN 10
+#define DBSDE_EXACT_GEO_ASIAN_PUT 11
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* hip_stream);
 
@@ -564,6 +603,13 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * d/dA_p = g', d/dS_d = g' (sum_n (double)fp32(J_{d,n} dt_n)) / (k T), J the DIAG
  * tangent.  L [k, k] (k <= 128) correlates the assets as for DIAG.  tau_p <= 0
  * returns g(A_p), 0 and (g', 0, .., 0).
+ * GEO_ASIAN (x [P, D] = [G_p, S_1..S_k]): ASIAN's threads and draws with
+ * I_d = sum_n (double)fp32(lg(S_{d,n}) dt_n), lg as in the scheme above; after the
+ * same reduction G_T = G_p exp((sum_d I_d) / (k T)) in fp64 and g(G_T) with one
+ * column.  delta: d/dG_p = g' G_T / G_p, d/dS_d = g' G_T (sum_n (double)fp32((J_{d,n}
+ * / S_{d,n}) dt_n)) / (k T).  L [k, k], k <= 128.  tau_p <= 0 returns g(G_p), 0 and
+ * (g', 0, .., 0).  Its exact value in continuous time is DBSDE_EXACT_GEO_ASIAN; the
+ * scheme differs from it by O(dt).
  *
  *   L       device [nb, nb] row-major lower Cholesky factor (the lower triangle is
  *           read), NULL = independent increments; DIAG: nb = D <= 128;
@@ -597,7 +643,8 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * or mc < 1; mc > 2^32; D > 4096; Heston with an odd D, with L or with delta;
  * L with D > 128; HESTON_CORR without L, with an odd D, with delta or with
  * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0; ASIAN with D < 2,
- * phi_c != 0, g_cols != 1, g_kind SUMSQ or LOG, or L with D - 1 > 128.  Needs no context;
+ * phi_c != 0, g_cols != 1, g_kind SUMSQ or LOG, or L with D - 1 > 128; GEO_ASIAN with any
+ * of those or sig_b != 0.  Needs no context;
  * the work is enqueued on hip_stream.
  */
 int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const float* L, const float* t, const float* x, int P,
