@@ -25,7 +25,8 @@ PROB_GEO_ASIAN = 8     # ProblemSpec(kind="diag", average="geometric"): state [G
 OPTIMIZERS = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3, "Adagrad": 4, "Adamax": 5, "Adadelta": 6, "ASGD": 7}
 EXACT_KINDS = {"bsb": 0, "bs_call": 1, "basket_avg": 2, "basket_mean": 3, "heston": 4,
                "bs_put": 5, "basket_avg_put": 6, "basket_mean_put": 7, "heston_put": 8,
-               "geo_asian": 10, "geo_asian_put": 11}   # (9 is no closed form)
+               "geo_asian": 10, "geo_asian_put": 11,   # (9 is no closed form; 12 and 13 are unknown)
+               "american_put": 14}                     # a binomial tree, not a closed form
 ABI_VERSION = 3
 
 # every symbol include/dbsde.h declares (checked by the CPU test suite)
@@ -48,7 +49,7 @@ class Problem(ctypes.Structure):
                 ("phi_zz", ctypes.c_float), ("g_kind", ctypes.c_int), ("strike", ctypes.c_float),
                 ("q3", ctypes.c_int), ("g_cols", ctypes.c_int), ("g_alpha", ctypes.c_float),
                 ("u_clamp", ctypes.c_int), ("h_kappa", ctypes.c_float), ("h_theta", ctypes.c_float),
-                ("h_sigma", ctypes.c_float), ("h_rho", ctypes.c_float)]
+                ("h_sigma", ctypes.c_float), ("h_rho", ctypes.c_float), ("pen", ctypes.c_float)]
 
 
 class Config(ctypes.Structure):

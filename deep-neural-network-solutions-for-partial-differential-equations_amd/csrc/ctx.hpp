@@ -53,6 +53,17 @@ inline const char* geo_asian_refusal(const dbsde_problem& pr, int D) {
   if (pr.sig_b != 0.f) return "the geometric-average problem needs sig_b == 0 (log S needs positive assets)";
   return nullptr;
 }
+// dbsde_problem.pen (the penalised American driver): why dbsde_create refuses
+// the problem, or null
+inline const char* pen_refusal(const dbsde_problem& pr) {
+  if (pr.pen == 0.f) return nullptr;
+  if (!(pr.pen > 0.f) || std::isinf(pr.pen)) return "pen must be finite and >= 0";
+  if (pr.kind != DBSDE_PROB_DIAG)
+    return "pen != 0 (the penalised American driver) is taken for DBSDE_PROB_DIAG only, not the Heston, Asian or "
+           "geometric-Asian kinds";
+  if (pr.u_clamp) return "pen != 0 cannot be combined with u_clamp";
+  return nullptr;
+}
 
 struct Lin {
   long long w = -1, b = -1;
@@ -218,6 +229,7 @@ struct dbsde_ctx {
         *G = nullptr;
   float* Pbuf[2] = {nullptr, nullptr};
   float *u = nullptr, *rres = nullptr, *lossrow = nullptr, *ubar = nullptr, *q3S = nullptr, *umask = nullptr;
+  float* dphidy = nullptr;               // [Rp] pen != 0, per-layer path: d phi / d Y of each interior row
   float *u16 = nullptr, *o16 = nullptr;  // [Rp,16]: col 0 = ubar / 1 (output-layer TN operands)
   double* loss_part = nullptr;
   float* loss_tmp = nullptr;

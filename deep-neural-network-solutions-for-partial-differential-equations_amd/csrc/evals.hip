@@ -6,10 +6,14 @@
 // include/dbsde.h (dbsde_exact, dbsde_hjb_mc); no context needed.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "../../include/dbsde.h"
 #include "philox.hpp"
+
+int fail(dbsde_ctx* c, int code, const std::string& msg);   // net.hip: the message dbsde_last_error(NULL) returns
 
 namespace dbsde {
 
@@ -144,6 +148,109 @@ __global__ void __launch_bounds__(256) geo_asian_exact_kernel(ExactArgs a) {
     float* dr = a.delta + r * a.D;
     dr[0] = (float)(fwd / G);
     for (int d = 1; d < a.D; ++d) dr[d] = tau > 0.0 ? (float)(fwd * tau / ((double)k * a.T * (double)xr[d])) : 0.f;
+  }
+}
+
+// --------------------------------------------------------------------------
+// DBSDE_EXACT_AMERICAN_PUT: the put with early exercise on a Cox-Ross-Rubinstein
+// tree in fp64 (include/dbsde.h): the arbiter of the penalised
+// problem, which no Feynman-Kac expectation prices.  One workgroup per (point,
+// coordinate); the level sits in LDS as doubles, node j of level i at
+// s u^{2j - i}.  Thread t owns the nodes j = t + 256 k, k < C = ceil((n + 1) /
+// 256) <= 17, so the 64 lanes of a wave touch 64 consecutive doubles (no bank
+// conflict), and keeps their prices and their own values in registers (one
+// multiplication by u per level).  A level step: every thread reads the upper
+// neighbour v[j + 1] of each of its nodes, barrier, writes its nodes' new
+// values, barrier.  No atomics, a fixed order: bitwise repeatable.
+//   pen = +inf:  v = max(c, g)                                  (American)
+//   pen finite:  v = g > c ? (c + pen Delta g) / (1 + pen Delta) : c
+// the implicit step of u' = .. + pen (g - u)^+ on the node, i.e. the value of
+// the penalised problem (pen = 0: the European tree).  A point whose
+// risk-neutral probability p = (e^{b Delta} - d) / (u - d) is not in [0, 1]
+// (a coarse tree: |b| sqrt(Delta) > sigma) has no tree value: price and delta
+// are NaN.
+// --------------------------------------------------------------------------
+constexpr int TREE_NMAX = 4096;
+constexpr int TREE_THREADS = 256;
+constexpr int TREE_CMAX = (TREE_NMAX + 1 + TREE_THREADS - 1) / TREE_THREADS;
+
+struct TreeArgs {
+  int D, n;
+  double T, r, sig, K, b, pen;
+  const float* t;
+  const float* x;
+  float* price;
+  float* delta;
+};
+
+__global__ void __launch_bounds__(TREE_THREADS) american_put_tree_kernel(TreeArgs a) {
+  __shared__ double v[TREE_NMAX + 1];
+  const long long i = blockIdx.x;   // (point, coordinate)
+  const int tid = threadIdx.x;
+  const double tau = a.T - (double)a.t[i / a.D];
+  const double S = (double)a.x[i], K = a.K;
+  if (tau <= 0.0) {   // the whole workgroup leaves together
+    if (tid == 0) {
+      a.price[i] = (float)(K - S > 0.0 ? K - S : 0.0);
+      if (a.delta) a.delta[i] = (float)(S < K ? -1.0 : (S == K ? -0.5 : 0.0));
+    }
+    return;
+  }
+  const int n = a.n;
+  const double dl = tau / (double)n, h = a.sig * sqrt(dl);
+  const double up = exp(h), dn = 1.0 / up;
+  const double p = (exp(a.b * dl) - dn) / (up - dn), q = 1.0 - p, disc = exp(-a.r * dl);
+  if (!(p >= 0.0 && p <= 1.0)) {   // (uniform over the workgroup, before any barrier)
+    if (tid == 0) {
+      a.price[i] = __builtin_nanf("");
+      if (a.delta) a.delta[i] = __builtin_nanf("");
+    }
+    return;
+  }
+  const bool amer = isinf(a.pen);
+  const double pd = amer ? 0.0 : a.pen * dl;
+  const int C = (n + TREE_THREADS) / TREE_THREADS;
+  double s[TREE_CMAX], w[TREE_CMAX];   // price and value of node tid + 256 k
+#pragma unroll
+  for (int k = 0; k < TREE_CMAX; ++k) {
+    const int j = tid + TREE_THREADS * k;
+    s[k] = w[k] = 0.0;
+    if (k < C && j <= n) {
+      s[k] = S * exp((double)(2 * j - n) * h);
+      w[k] = K - s[k] > 0.0 ? K - s[k] : 0.0;
+      v[j] = w[k];
+    }
+  }
+  __syncthreads();
+  double v10 = 0.0, v11 = 0.0;
+  for (int lv = n - 1; lv >= 0; --lv) {
+    double hi[TREE_CMAX];
+#pragma unroll
+    for (int k = 0; k < TREE_CMAX; ++k) {
+      const int j = tid + TREE_THREADS * k;
+      hi[k] = (k < C && j <= lv) ? v[j + 1] : 0.0;   // j + 1 <= lv + 1 <= n
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < TREE_CMAX; ++k) {
+      const int j = tid + TREE_THREADS * k;
+      if (k < C && j <= lv) {
+        s[k] *= up;
+        const double c = disc * (p * hi[k] + q * w[k]);
+        const double g = K - s[k] > 0.0 ? K - s[k] : 0.0;
+        w[k] = amer ? (c > g ? c : g) : (g > c ? (c + pd * g) / (1.0 + pd) : c);
+        v[j] = w[k];
+      }
+    }
+    __syncthreads();
+    if (lv == 1 && tid == 0) {
+      v10 = v[0];
+      v11 = v[1];
+    }
+  }
+  if (tid == 0) {
+    a.price[i] = (float)v[0];
+    if (a.delta) a.delta[i] = (float)((v11 - v10) / (S * up - S * dn));
   }
 }
 
@@ -363,8 +470,9 @@ extern "C" {
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* stream) {
   const bool geo = kind == DBSDE_EXACT_GEO_ASIAN || kind == DBSDE_EXACT_GEO_ASIAN_PUT;
-  if (kind < DBSDE_EXACT_BSB || (kind > DBSDE_EXACT_HESTON_PUT && !geo) || !t || !x || !params || !price || R < 1 ||
-      D < 1)
+  const bool tree = kind == DBSDE_EXACT_AMERICAN_PUT;
+  if (kind < DBSDE_EXACT_BSB || (kind > DBSDE_EXACT_HESTON_PUT && !geo && !tree) || !t || !x || !params || !price ||
+      R < 1 || D < 1)
     return DBSDE_EINVAL;
   if (geo && D < 2) return DBSDE_EINVAL;   // x = [G, S_1..S_k]
   // the kernels read and write whole floats: an address that is no multiple of
@@ -374,6 +482,32 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
   if (misaligned(t, sizeof(float)) || misaligned(x, sizeof(float)) || misaligned(price, sizeof(float)) ||
       misaligned(delta, sizeof(float)) || misaligned(params, sizeof(double)))
     return DBSDE_EINVAL;
+  if (tree) {   // params = {r, sigma, K, b, n_tree, pen}; price and delta [R, D]
+    auto bad = [](const std::string& m) { return fail(nullptr, DBSDE_EINVAL, "dbsde_exact(DBSDE_EXACT_AMERICAN_PUT): " + m); };
+    const double nt = params[4], pen = params[5];
+    if (!(params[1] > 0.0) || !std::isfinite(params[1])) return bad("sigma must be > 0");
+    if (!(params[2] > 0.0) || !std::isfinite(params[2])) return bad("K must be > 0");
+    if (!std::isfinite(params[0]) || !std::isfinite(params[3])) return bad("r and b must be finite");
+    if (!(nt >= 2.0 && nt <= (double)TREE_NMAX) || nt != std::floor(nt))
+      return bad("n_tree must be an integer in [2, 4096]");
+    if (!(pen >= 0.0)) return bad("pen must be >= 0 (+inf: the American value), not negative or NaN");
+    if (R > 0x7fffffffLL / D) return bad("R * D must be below 2^31 (one workgroup per point and coordinate)");
+    TreeArgs g{};
+    g.D = D;
+    g.n = (int)nt;
+    g.T = T;
+    g.r = params[0];
+    g.sig = params[1];
+    g.K = params[2];
+    g.b = params[3];
+    g.pen = pen;
+    g.t = t;
+    g.x = x;
+    g.price = price;
+    g.delta = delta;
+    american_put_tree_kernel<<<(unsigned)(R * D), TREE_THREADS, 0, (hipStream_t)stream>>>(g);
+    return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
+  }
   if (geo) {   // params = {mu, r, sigma, K, cbar, vbar}; delta [R, D]
     if ((R + 255) / 256 > 0x7fffffffLL) return DBSDE_EINVAL;
     ExactArgs g{};

@@ -21,6 +21,7 @@ struct CotanParams {
   float phi_r, phi_c, phi_zz, strike, g_alpha;
   float gsign;              // -1: put (g_kind holds the call kind, terminal_kind)
   int g_kind;
+  float pen;                // dbsde_problem.pen: phi -= pen max(g(X) - Y, 0) (kernels.hpp penalty_phi)
   // net_u VJP (dbsde_net_u_vjp): caller cotangents instead of the BSDE
   // residual ones -- ubar from ext_ub [Rp], zbar from the sdw rows
   int ext;
@@ -160,11 +161,19 @@ __device__ __forceinline__ void zero(Mat<TT>& m) {
 }
 
 // residual of a non-terminal row from its row sums rs, Y = y, Y_next = yn,
-// dt and the Q3 sum: Y_{n+1} - Ytilde_{n+1} (DeepBSDE.py:223-228)
+// dt and the Q3 sum: Y_{n+1} - Ytilde_{n+1} (DeepBSDE.py:223-228); dphidy
+// receives the row's d phi / d Y (phi_r, plus the penalty's indicator: g from
+// the row's own s_x, s_xx)
 __device__ __forceinline__ float step_residual(const CotanParams& p, floatx4 rs0, floatx4 rs1, float y, float yn,
-                                               float dt, float q3) {
+                                               float dt, float q3, float& dphidy) {
   const float zs = p.q3S ? rs1[1] * q3 : rs0[0];
-  const float phi = p.phi_r * (y - p.phi_c * rs0[1]) + p.phi_zz * rs0[2];
+  float phi = p.phi_r * (y - p.phi_c * rs0[1]) + p.phi_zz * rs0[2];
+  dphidy = p.phi_r;
+  if (p.pen != 0.f) {
+    float gs, dy;
+    phi += penalty_phi(p.pen, terminal_g(p.g_kind, rs0[3], rs1[0], p.gcols, p.strike, p.g_alpha, p.gsign, gs), y, dy);
+    dphidy = p.phi_r + dy;
+  }
   return yn - (y + phi * dt + zs);
 }
 
@@ -200,11 +209,13 @@ __device__ __forceinline__ RowCotan row_cotan(const CotanParams& p, int r) {
     c.gB = (p.g_kind == 0 || p.g_kind == 3) ? 0.f : c.gsc;
   } else {
     c.dt = tn - t;
-    c.res = step_residual(p, a0, a1, y, yn, c.dt, q);
-    c.ub = -2.f * c.res * (1.f + p.phi_r * c.dt);
+    float dy;
+    c.res = step_residual(p, a0, a1, y, yn, c.dt, q, dy);
+    c.ub = -2.f * c.res * (1.f + dy * c.dt);
     c.q3s = q;
   }
-  if (n >= 1) c.ub += 2.f * step_residual(p, b0, b1, yp, y, t - tp, qp);
+  float dyp;   // (the previous row's own factor is that row's business)
+  if (n >= 1) c.ub += 2.f * step_residual(p, b0, b1, yp, y, t - tp, qp, dyp);
   c.ub *= c.mask;
   c.coefY = -2.f * c.res;
   if (!c.valid) c.res = c.ub = c.coefY = 0.f;   // padding rows carry no cotangent
@@ -270,6 +281,7 @@ struct ZRowArgs {
   float* zbar;          // [Rp, Dp]
   float* rres;          // [Rp]
   float* lossrow;       // [Rp]
+  float* dphidy;        // [Rp] pen != 0: the row's d phi / d Y, for ubar_kernel
 };
 __global__ void __launch_bounds__(256) zrow_cotan_kernel(ZRowArgs a) {
   const CotanParams& p = a.p;
@@ -308,7 +320,9 @@ __global__ void __launch_bounds__(256) zrow_cotan_kernel(ZRowArgs a) {
     if (!c.term) {
       c.dt = xr[p.Dp] - xr[0];
       c.q3s = p.q3S ? p.q3S[c.n] : 0.f;
-      c.res = step_residual(p, rs0, rs1, y, p.u[r + 1], c.dt, c.q3s);
+      float dy;
+      c.res = step_residual(p, rs0, rs1, y, p.u[r + 1], c.dt, c.q3s, dy);
+      if (p.pen != 0.f && sub == 0) a.dphidy[r] = dy;
       c.coefY = -2.f * c.res;
     } else {
       c.res = y - terminal_g(p.g_kind, rs0[3], rs1[0], p.gcols, p.strike, p.g_alpha, p.gsign, c.gsc);

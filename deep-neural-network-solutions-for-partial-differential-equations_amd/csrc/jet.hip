@@ -338,6 +338,7 @@ struct PdeArgs {
   float rhob;              // HESTON2: fp32(sqrt(1 - (double)h_rho^2))
   int asian;               // 1 DBSDE_PROB_ASIAN: state [A, S_1..S_nb] (heston = 0); 2 DBSDE_PROB_GEO_ASIAN: [G, S]
   float T;                 // its averaging horizon
+  int gcols;               // leading state columns entering g (pr.pen != 0: the penalty's g)
   const float* Lt;      // [nb][nb] L^T (dbsde_set_corr) or null
   const float* X;
   long long r0;          // the chunk's first point
@@ -423,6 +424,17 @@ __global__ void __launch_bounds__(256) pde_terms_kernel(PdeArgs a) {
   const float* x = a.X + (size_t)p * D;
   const float* du = a.Du + (size_t)p * D;
   float drift = 0.f, xz = 0.f, zz = 0.f;
+  // pr.pen != 0 (DIAG only): g of the point's own x for the penalty term, its
+  // sums taken on this walk of the row
+  float s_x = 0.f, s_xx = 0.f;
+  if (a.pr.pen != 0.f) {
+    for (int d = lane; d < a.gcols; d += 64) {
+      s_x += x[d];
+      s_xx += x[d] * x[d];
+    }
+    s_x = wave_sum(s_x);
+    s_xx = wave_sum(s_xx);
+  }
   const int k = a.heston == 2 ? D >> 1 : a.nb;   // assets of a Heston state
   for (int d = lane; d < D; d += 64) {
     const float xd = x[d], zd = du[d];
@@ -462,7 +474,12 @@ __global__ void __launch_bounds__(256) pde_terms_kernel(PdeArgs a) {
   const float u = a.u[p];
   const float ut = a.d1[r * a.nd];
   const float diff = 0.5f * tr;
-  const float phi = a.pr.phi_r * (u - a.pr.phi_c * xz) + a.pr.phi_zz * zz;
+  float phi = a.pr.phi_r * (u - a.pr.phi_c * xz) + a.pr.phi_zz * zz;
+  if (a.pr.pen != 0.f) {   // the penalised PDE's driver (kernels.hpp penalty_phi)
+    float gsign, gs, dy;
+    const int gk = terminal_kind(a.pr.g_kind, gsign);
+    phi += penalty_phi(a.pr.pen, terminal_g(gk, s_x, s_xx, a.gcols, a.pr.strike, a.pr.g_alpha, gsign, gs), u, dy);
+  }
   if (a.out.u) a.out.u[p] = u;
   if (a.out.u_t) a.out.u_t[p] = ut;
   if (a.out.drift) a.out.drift[p] = drift;
@@ -700,6 +717,7 @@ int dbsde_pde_residual(dbsde_ctx* c, const float* params, int R, const float* t,
     pa.rhob = c->rhob;
     pa.asian = c->geo ? 2 : (c->asian ? 1 : 0);
     pa.T = c->cfg.T;
+    pa.gcols = c->gcols;
     pa.D = D;
     pa.nb = c->nb;
     pa.nd = nd;

@@ -138,6 +138,20 @@ __device__ __forceinline__ float terminal_dg(int kind, float x, float gsc) {
 }
 
 // --------------------------------------------------------------------------
+// The Y-nonlinear part of the driver (dbsde_problem.pen): the
+// penalised American problem adds -pen max(g(X) - Y, 0) to phi, g the terminal
+// condition on the row's own X, and pen 1[g > Y] to d phi / d Y (strict: 0 at a
+// tie, as torch.relu's gradient).  Returns the term; dphidy receives what
+// d phi / d Y gains.  Every caller sits inside `if (pen != 0.f)` on the kernel
+// argument, so a problem without a penalty runs none of this.
+// --------------------------------------------------------------------------
+__device__ __forceinline__ float penalty_phi(float pen, float g, float y, float& dphidy) {
+  const bool ex = g > y;
+  dphidy = ex ? pen : 0.f;
+  return ex ? -(pen * (g - y)) : 0.f;
+}
+
+// --------------------------------------------------------------------------
 // Chain GEMM:  C[Rp, NP] = A[Rp, K] * Bt[NP, K]^T  with a fused epilogue.
 // fp32 MFMA v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulate).
 // Workgroup: 4 waves, 64 rows x (16*NT) columns; each wave 16 rows x 16*NT.
@@ -184,6 +198,8 @@ struct ChainArgs {
   float phi_r, phi_c, phi_zz, strike, g_alpha;
   float gsign;        // -1: put (g_kind holds the call kind, terminal_kind)
   int g_kind, gcols;
+  float pen;          // dbsde_problem.pen (penalty_phi)
+  float* dphidy;      // [Rp] pen != 0: the row's d phi / d Y = phi_r + pen 1[g > Y], for ubar_kernel
   float* zbar;        // [Rp, ldx]
   float* rres;        // [Rp]
   float* lossrow;     // [Rp]
@@ -328,7 +344,12 @@ __global__ void __launch_bounds__(256) chain_gemm_kernel(ChainArgs p) {
           // Q3 (D == 1, 1d_BSPDE_case.py:271-273): Z_i * sum_j (sigma dW)_j
           if (p.q3S) S = p.q3S[n];
           const float zs = p.q3S ? z1 * S : s_zs;
-          const float phi = p.phi_r * (y - p.phi_c * s_xz) + p.phi_zz * s_zz;
+          float phi = p.phi_r * (y - p.phi_c * s_xz) + p.phi_zz * s_zz;
+          if (p.pen != 0.f) {   // the row's own g, from the sums it already holds
+            float gs, dy;
+            phi += penalty_phi(p.pen, terminal_g(p.g_kind, s_x, s_xx, G, p.strike, p.g_alpha, p.gsign, gs), y, dy);
+            if (cl == 0) p.dphidy[row] = p.phi_r + dy;
+          }
           const float ytil = y + phi * dt + zs;
           res = p.u[row + 1] - ytil;
           lossv = res * res;
@@ -450,7 +471,8 @@ __global__ void __launch_bounds__(256) rowdot_kernel(const float* H, int ldh, in
 #ifndef DBSDE_DEVICE_HELPERS_ONLY
 __global__ void __launch_bounds__(256) ubar_kernel(const float* rres, const float* xin, int ldx, int R, int Rp,
                                                    int N1, float phi_r, const float* lossrow, float* ubar,
-                                                   float* u16, double* loss_part, const float* umask) {
+                                                   float* u16, double* loss_part, const float* umask,
+                                                   const float* dphidy) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   float ub = 0.f;
   double lv = 0.0;
@@ -459,7 +481,8 @@ __global__ void __launch_bounds__(256) ubar_kernel(const float* rres, const floa
     if (n >= 1) ub += 2.f * rres[row - 1];
     if (n < N1 - 1) {
       const float dt = xin[(size_t)(row + 1) * ldx] - xin[(size_t)row * ldx];
-      ub += -2.f * rres[row] * (1.f + phi_r * dt);
+      // dphidy (pen != 0): the interior row's d phi / d Y as its cotangent kernel wrote it
+      ub += -2.f * rres[row] * (1.f + (dphidy ? dphidy[row] : phi_r) * dt);
     } else {
       ub += 2.f * rres[row];
     }

@@ -537,6 +537,9 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_PUT) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
     return bad("phi_zz != 0 is not a linear problem (no Feynman-Kac expectation); the HJB comparator is dbsde_hjb_mc");
+  if (prob->pen != 0.f)
+    return bad("pen != 0 is not a linear problem (no Feynman-Kac expectation); the arbiter of the penalised American "
+               "put is dbsde_exact's DBSDE_EXACT_AMERICAN_PUT");
   const bool heston2 = prob->kind == DBSDE_PROB_HESTON2;   // the same state and the same refusals
   const bool hcorr = prob->kind == DBSDE_PROB_HESTON_CORR;   // kind HESTON's process, its assets correlated by L
   const bool heston = prob->kind == DBSDE_PROB_HESTON || heston2 || hcorr;

@@ -293,6 +293,7 @@ int build_net(dbsde_ctx* c) {
     if (const char* why = c->geo ? geo_asian_refusal(pr, c->D) : asian_refusal(pr, c->D))
       return fail(c, DBSDE_EINVAL, why);
   }
+  if (const char* why = pen_refusal(pr)) return fail(c, DBSDE_EINVAL, why);
   if ((c->heston || c->heston2) && c->D % 2 != 0)
     return fail(c, DBSDE_EINVAL, "Heston state is [S_1..S_k, v_1..v_k]: layers[0] - 1 must be even");
   // two-factor Heston: |rho| <= 1, and the v-column weight of the second Brownian motion
@@ -666,6 +667,7 @@ int ensure_rows(dbsde_ctx* c, int Rp, int N) {
   if ((rc = dalloc_t(c, &c->u, R + 64))) return rc;
   if ((rc = dalloc_t(c, &c->rres, R))) return rc;
   if ((rc = dalloc_t(c, &c->lossrow, R))) return rc;
+  if (c->cfg.problem.pen != 0.f && (rc = dalloc_t(c, &c->dphidy, R))) return rc;
   if ((rc = dalloc_t(c, &c->ubar, R))) return rc;
   if ((rc = dalloc_t(c, &c->umask, R))) return rc;
   if ((rc = dalloc_t(c, &c->u16, R * 16))) return rc;

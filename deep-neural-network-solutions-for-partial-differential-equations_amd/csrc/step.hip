@@ -447,6 +447,7 @@ CotanParams cotan_params(dbsde_ctx* c, int R, int Rp, int N1, bool q3) {
   p.strike = pr.strike;
   p.g_alpha = pr.g_alpha;
   p.g_kind = terminal_kind(pr.g_kind, p.gsign);
+  p.pen = pr.pen;
   return p;
 }
 
@@ -977,6 +978,7 @@ int loss_grad_impl(dbsde_ctx* c, const float* params, const dbsde_batch* b, floa
       za.zbar = c->zbar;
       za.rres = c->rres;
       za.lossrow = c->lossrow;
+      za.dphidy = c->dphidy;
       RUN(c, s, "z_row_cotangent", 12.0 * R * D, 4.0 * R * (5.0 * c->Dp),
           zrow_cotan_kernel<<<Rp / 16, 256, 0, s>>>(za));
     } else {
@@ -998,6 +1000,8 @@ int loss_grad_impl(dbsde_ctx* c, const float* params, const dbsde_batch* b, floa
       a.g_alpha = pr.g_alpha;
       a.g_kind = terminal_kind(pr.g_kind, a.gsign);
       a.gcols = c->gcols;
+      a.pen = pr.pen;
+      a.dphidy = c->dphidy;
       a.zbar = c->zbar;
       a.rres = c->rres;
       a.lossrow = c->lossrow;
@@ -1007,7 +1011,8 @@ int loss_grad_impl(dbsde_ctx* c, const float* params, const dbsde_batch* b, floa
     }
     RUN(c, s, "ubar_loss", 0.0, 16.0 * R,
         ubar_kernel<<<Rp / 256 + 1, 256, 0, s>>>(c->rres, c->xin, c->Dp, R, Rp, N1, pr.phi_r, c->lossrow, c->ubar,
-                                                 c->u16, c->loss_part, c->u_clamp ? c->umask : nullptr));
+                                                 c->u16, c->loss_part, c->u_clamp ? c->umask : nullptr,
+                                                 pr.pen != 0.f ? c->dphidy : nullptr));
     nloss_parts = Rp / 256 + 1;
   }
   float* loss_dst = (out && out->loss) ? out->loss : c->loss_tmp;

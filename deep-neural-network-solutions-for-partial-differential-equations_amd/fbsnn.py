@@ -843,6 +843,9 @@ class FBSNN(ABC):
         spec = self.problem_spec()
         if spec.phi_zz != 0:
             raise ValueError(f"{type(self).__name__} is not linear (phi_zz != 0): its comparator is hjb_mc")
+        if spec.penalty != 0:
+            raise ValueError(f"{type(self).__name__} is not linear (penalty != 0): its arbiter is tree_value "
+                             "(european().mc_value is the lower bound)")
         X = self._mc_state(X)
         t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1).contiguous()
         L = self._L if (self._L is not None and spec.kind in ("diag", "heston")) else None

@@ -69,8 +69,12 @@ def spec_functions(spec, strike=None, T=None):
         return torch.diag_embed(spec.sig_a * X + spec.sig_b)
 
     def phi(t, X, Y, Z):
-        return spec.phi_r * (Y - spec.phi_c * torch.sum(X * Z, dim=1, keepdim=True)) + \
+        lin = spec.phi_r * (Y - spec.phi_c * torch.sum(X * Z, dim=1, keepdim=True)) + \
             spec.phi_zz * torch.sum(Z * Z, dim=1, keepdim=True)
+        pen = float(getattr(spec, "penalty", 0.0))
+        if pen == 0.0:
+            return lin
+        return lin - pen * torch.relu(g(X) - Y)      # the penalised American driver (dbsde_problem.pen)
 
     def g(X):
         S = cols(X)

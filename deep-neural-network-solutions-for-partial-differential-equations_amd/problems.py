@@ -20,6 +20,9 @@ methods (generic.py) instead of silently training the parent's problem.
   GeometricAsianCallOption / GeometricAsianPutOption, GeometricAsianBasketCallOption /
   GeometricAsianBasketPutOption
                         (no reference counterpart)      geometric-average options, with a closed form
+  AmericanPutOption / AmericanBasketPutOption
+                        (no reference counterpart)      PutOption / BasketPutOption with early exercise,
+                                                        by penalisation: phi -= penalty (g(X) - Y)^+
   BlackScholesBarenblatt: see deepbsde.py (DeepBSDE.py:326-341 surface)
 """
 from __future__ import annotations
@@ -623,7 +626,124 @@ class GeometricAsianBasketPutOption(GeometricAsianBasketCallOption):
     option_type = "put"
 
 
+class _AmericanPut:
+    """Early exercise by penalisation (dbsde_problem.pen): the
+    parent's put with the driver
+
+      phi = phi_parent - penalty max(g(X) - Y, 0),
+
+    g the parent's payoff on the row's own X, i.e. the semilinear PDE
+    u_t + L u - phi_lin + penalty (g - u)^+ = 0, u(T, .) = g, whose solution
+    rises to the American value as penalty grows (at penalty = 100, the
+    default, about 2 % of the early-exercise premium is missing at the money,
+    K = 1, r = 0.05, sigma = 0.2, T = 1).  problem_spec() carries the penalty,
+    so the problem runs in the kernels; a subclass that changes phi_tf runs its
+    own methods (generic.py) like any other.  Not linear: mc_value raises;
+    the arbiter is tree_value (one asset).  european() is the same problem
+    without the penalty, whose mc_value and closed_form bound it from below."""
+
+    def __init__(self, *args, penalty=100.0, **kw):
+        penalty = float(penalty)
+        if not (penalty >= 0.0 and math.isfinite(penalty)):
+            raise ValueError("penalty must be finite and >= 0")
+        self.penalty = penalty
+        self._ctor = (args, dict(kw))
+        super().__init__(*args, **kw)
+
+    def problem_spec(self):
+        return dataclasses.replace(super().problem_spec(), penalty=self.penalty)
+
+    def phi_tf(self, t, X, Y, Z):
+        return super().phi_tf(t, X, Y, Z) - self.penalty * torch.relu(self.g_tf(X) - Y)
+
+    def european(self):
+        """The same problem with penalty = 0: a new object built from this one's
+        constructor arguments, with its own (freshly initialised) network and
+        this object's correlation -- correlation_matrix, the Cholesky factor _L
+        and the native context's copy are taken from self, not drawn again, so
+        its mc_value prices the same correlated basket.  The caller's numpy and
+        torch (CPU) random streams are left where they were."""
+        args, kw = self._ctor
+        np_state, torch_state = np.random.get_state(), torch.get_rng_state()
+        try:
+            twin = type(self)(*args, penalty=0.0, **kw)
+        finally:
+            np.random.set_state(np_state)
+            torch.set_rng_state(torch_state)
+        twin.correlation_matrix = np.array(self.correlation_matrix, copy=True)
+        twin._L = None if self._L is None else np.array(self._L, copy=True)
+        if twin._L is not None:
+            twin.solver.set_corr(twin._L)
+        return twin
+
+    def _one_asset(self, what):
+        if self.D != 1:
+            raise ValueError(f"{what} prices one asset (D = 1); this object has D = {self.D}")
+        spec = self.problem_spec()
+        # r, sigma, K and the risk-neutral drift b of the simulated asset
+        return spec.phi_r, spec.sig_a, float(self.strike), spec.mu_a + spec.phi_r * spec.phi_c
+
+    def _tx(self, t, X):
+        X = torch.as_tensor(np.asarray(X) if not isinstance(X, torch.Tensor) else X,
+                            dtype=torch.float32).to(self.device).reshape(-1, 1).contiguous()
+        t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t,
+                            dtype=torch.float32).to(self.device).reshape(-1).contiguous()
+        if t.numel() != X.shape[0]:
+            raise ValueError("t and X must hold the same number of points")
+        return t, X
+
+    def tree_value(self, t, X, n_tree=2000, penalised=False):
+        """(price [R, 1], delta [R, 1]) of this object's put with early exercise
+        at the points (t [R], X [R, 1]) on a binomial tree of n_tree steps
+        (exact("american_put"), DBSDE_EXACT_AMERICAN_PUT) with the object's r,
+        sigma, strike and drift b = mu_a + phi_r phi_c.  penalised=False: the
+        American value; True: the value of the penalised problem the network
+        trains on (this object's penalty).  One asset only."""
+        r, sigma, K, b = self._one_asset("tree_value")
+        t, X = self._tx(t, X)
+        return _exact("american_put", t, X, self.T, r, sigma, K, b=b, n_tree=n_tree,
+                      penalty=self.penalty if penalised else math.inf)
+
+    def closed_form(self, t, X):
+        """The European put's Black-Scholes value with cost of carry b at the
+        points: (price [R, 1], delta [R, 1]), evaluated in float64 and returned
+        as float32 tensors on the device.  It is the solution of the penalty = 0
+        problem only: an object with penalty > 0 raises ValueError (its problem
+        has no closed form; european().closed_form is its lower bound and
+        tree_value its arbiter).  One asset only."""
+        if self.penalty != 0.0:
+            raise ValueError(f"{type(self).__name__} with penalty > 0 has no closed form: european().closed_form "
+                             "is the European lower bound, tree_value the American value")
+        r, sigma, K, b = self._one_asset("closed_form")
+        t, X = self._tx(t, X)
+        S, tau = X[:, 0].double(), self.T - t.double()
+        live = tau > 0
+        tl = torch.where(live, tau, torch.ones_like(tau))
+        st = sigma * torch.sqrt(tl)
+        d1 = (torch.log(S / K) + (b + 0.5 * sigma * sigma) * tl) / st
+        N = lambda v: 0.5 * torch.erfc(-v / math.sqrt(2.0))
+        carry = torch.exp((b - r) * tl)
+        price = K * torch.exp(-r * tl) * N(-(d1 - st)) - S * carry * N(-d1)
+        delta = -carry * N(-d1)
+        pay = torch.clamp(K - S, min=0.0)
+        dpay = torch.where(S < K, -torch.ones_like(S), torch.where(S == K, -0.5 * torch.ones_like(S), torch.zeros_like(S)))
+        price, delta = torch.where(live, price, pay), torch.where(live, delta, dpay)
+        return price.float().reshape(-1, 1), delta.float().reshape(-1, 1)
+
+
+class AmericanPutOption(_AmericanPut, PutOption):
+    """PutOption (payoff max(K - sum X, 0), phi = r (Y - X.Z)) with early exercise
+    by penalisation, on PutOption's surface; keyword penalty=100.0."""
+
+
+class AmericanBasketPutOption(_AmericanPut, BasketPutOption):
+    """BasketPutOption (payoff max(K - mean X, 0), correlated increments, its
+    schedule and train surface) with early exercise by penalisation; keyword
+    penalty=100.0.  No multi-asset arbiter: tree_value needs D = 1."""
+
+
 __all__ = ["CallOption", "PutOption", "CallOption1D", "BasketCallOption", "BasketPutOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN", "HestonTwoFactorFBSNN", "AsianCallOption", "AsianPutOption", "AsianBasketCallOption",
            "AsianBasketPutOption", "GeometricAsianCallOption", "GeometricAsianPutOption",
-           "GeometricAsianBasketCallOption", "GeometricAsianBasketPutOption"]
+           "GeometricAsianBasketCallOption", "GeometricAsianBasketPutOption", "AmericanPutOption",
+           "AmericanBasketPutOption"]

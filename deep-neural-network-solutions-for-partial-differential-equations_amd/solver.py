@@ -7,6 +7,7 @@ torch's current stream.
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 
 import torch
@@ -32,7 +33,10 @@ class ProblemSpec:
     is on A alone (g_cols = 1, a call or put g, phi_c = 0).  average is False,
     True or "arithmetic" (the same), or "geometric": DBSDE_PROB_GEO_ASIAN --
     state [G, S_1..S_k], G the running geometric average
-    exp((1/T) int mean_i log S_i dt), G_0 = 1, sig_b = 0; the payoff is on G."""
+    exp((1/T) int mean_i log S_i dt), G_0 = 1, sig_b = 0; the payoff is on G.
+    penalty (kind "diag" without an average and without u_clamp only): lambda
+    >= 0 of the penalised American problem, phi -= penalty max(g(X) - Y, 0)
+    with g on the row's own X (dbsde_problem.pen); 0 is the European problem."""
 
     mu_a: float = 0.0
     sig_a: float = 0.0
@@ -51,6 +55,7 @@ class ProblemSpec:
     theta: float = 0.0
     sigma: float = 0.0
     rho: float = 0.0
+    penalty: float = 0.0
     average: bool = False
 
     def average_kind(self):
@@ -72,10 +77,19 @@ class ProblemSpec:
                              "not supported")
         kind = {None: _lib.PROBLEM_KINDS[self.kind], "arithmetic": _lib.PROB_ASIAN,
                 "geometric": _lib.PROB_GEO_ASIAN}[average]
+        pen = float(self.penalty)
+        if pen != 0.0:
+            if not (pen > 0.0 and math.isfinite(pen)):
+                raise ValueError(f"penalty must be finite and >= 0, not {self.penalty!r}")
+            if self.kind != "diag" or average:
+                raise ValueError("a non-zero penalty (the penalised American problem) needs kind 'diag' without an "
+                                 "average: Heston and Asian states are not supported")
+            if self.u_clamp:
+                raise ValueError("a non-zero penalty cannot be combined with u_clamp")
         return _lib.Problem(kind, self.mu_a, self.sig_a, self.sig_b, self.phi_r,
                             self.phi_c, self.phi_zz, _lib.G_KINDS[self.g], self.strike, int(self.q3),
                             int(self.g_cols), self.g_alpha, int(self.u_clamp), self.kappa, self.theta,
-                            self.sigma, self.rho)
+                            self.sigma, self.rho, pen)
 
 
 def _ptr(t):
@@ -425,7 +439,7 @@ def free_call_profile(enable=None, reset=False):
     return out
 
 
-def exact(kind, t, X, T, params):
+def exact(kind, t, X, T, params=(), sigma=None, K=None, *, b=None, n_tree=None, penalty=None):
     """Device exact / comparator solutions (include/dbsde.h dbsde_exact):
     kind in {"bsb", "bs_call", "basket_avg", "basket_mean", "heston"}; t [R],
     X [R, D] float32 cuda tensors.  Returns (price, delta); delta is None for
@@ -437,10 +451,40 @@ def exact(kind, t, X, T, params):
     "geo_asian_put": the options on the geometric average in continuous time,
     X [R, 1 + k] = [G, S_1..S_k], T the averaging horizon, params = (mu, r,
     sigma, K, cbar, vbar) (cbar = mean diag(L L^T), vbar = 1^T L L^T 1 / k^2;
-    1 and 1 / k without a factor), price [R, 1], delta [R, 1 + k]."""
+    1 and 1 / k without a factor), price [R, 1], delta [R, 1 + k].
+    params is one sequence.  sigma, K, b, n_tree and penalty belong to
+    "american_put" alone: any other kind given one of them raises ValueError.
+
+    exact("american_put", t, X, T, r, sigma, K, b=None, n_tree=2000,
+    penalty=math.inf) -- r in params' place, or params = (r, sigma, K) with
+    sigma and K left out: the put max(K - s, 0) with early exercise on every
+    coordinate of X [R, D] by a Cox-Ross-Rubinstein tree of n_tree (an integer
+    in [2, 4096], else ValueError) steps in fp64 (DBSDE_EXACT_AMERICAN_PUT),
+    price and delta [R, D].  b is the risk-neutral drift of the asset (None:
+    r).  penalty = inf is the American value v = max(c, g); a finite penalty
+    >= 0 the value of the penalised problem a ProblemSpec(penalty=...) trains
+    on (0: the European tree).  A point whose risk-neutral probability
+    (e^{b dt} - d) / (u - d) leaves [0, 1] (a coarse tree, |b| sqrt(dt) > sigma)
+    has no tree value: its price and delta are NaN."""
     lib = _lib.load()
     if kind not in _lib.EXACT_KINDS:
         raise ValueError(f"unknown exact solution {kind!r}")
+    tree = kind == "american_put"
+    if tree:
+        if sigma is None and K is None:
+            if not hasattr(params, "__len__") or len(params) != 3:
+                raise ValueError("'american_put' takes r, sigma, K (and b=, n_tree=, penalty=)")
+            r_, sigma, K = params
+        elif sigma is None or K is None or hasattr(params, "__len__"):
+            raise ValueError("'american_put' takes r, sigma, K (and b=, n_tree=, penalty=)")
+        else:
+            r_ = params
+        nt = float(2000 if n_tree is None else n_tree)
+        if not (math.isfinite(nt) and nt == math.floor(nt) and 2 <= nt <= 4096):
+            raise ValueError("n_tree must be an integer in [2, 4096]")
+        params = (r_, sigma, K, r_ if b is None else b, nt, float(math.inf if penalty is None else penalty))
+    elif any(v is not None for v in (sigma, K, b, n_tree, penalty)):
+        raise ValueError(f"sigma, K, b, n_tree and penalty are arguments of 'american_put', not of {kind!r}")
     X = X.reshape(X.shape[0], -1).contiguous().float()
     t = t.reshape(-1).contiguous().float()
     R, D = X.shape
@@ -450,12 +494,12 @@ def exact(kind, t, X, T, params):
     geo = kind in ("geo_asian", "geo_asian_put")
     if geo and D < 2:
         raise ValueError(f"{kind!r} takes X [R, 1 + k] = [G, S_1..S_k]")
-    ncol = D if kind in ("bs_call", "bs_put") else 1
+    ncol = D if kind in ("bs_call", "bs_put", "american_put") else 1
     price = torch.empty((R, ncol), device=X.device)
     delta = None if kind == "bsb" else torch.empty((R, D if geo else ncol), device=X.device)
     import numpy as np
     p = np.zeros(6, dtype=np.float64)
-    if len(params) > (6 if heston or geo else 3):
+    if len(params) > (6 if heston or geo or tree else 3):
         raise ValueError(f"too many parameters for {kind!r}")
     if heston and len(params) != 6:
         raise ValueError(f"{kind!r} takes params = (r, K, kappa, theta, sigma, rho)")
@@ -501,6 +545,9 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
     estimator (diag only)."""
     if spec.phi_zz != 0:
         raise ValueError("mc_value needs a linear problem (phi_zz == 0); the HJB comparator is hjb_mc")
+    if spec.penalty != 0:
+        raise ValueError("mc_value needs a linear problem (penalty == 0); the arbiter of the penalised American put "
+                         "is exact('american_put') (DBSDE_EXACT_AMERICAN_PUT)")
     if L is not None:   # the checks that need no device
         import numpy as np
         L = np.ascontiguousarray(np.asarray(L.cpu() if isinstance(L, torch.Tensor) else L, dtype=np.float32))

@@ -171,6 +171,24 @@ extern "C" {
  *   u_clamp  = 1: u = max(net(t, X), 0) (heston_dnnpde.py:568)
  *   q3       = 1: for D == 1 reproduce the reference's squeeze() broadcast in
  *              the Y-tilde term (1d_BSPDE_case.py:271-273)
+ *   pen      = lambda >= 0, the penalty of the penalised American problem
+ *                u_t + mu.Du + 1/2 tr(sigma sigma^T D^2 u) - phi_lin + pen (g(x) - u)^+ = 0,  u(T, .) = g:
+ *              the driver becomes  phi = phi_r (Y - phi_c X.Z) + phi_zz |Z|^2 - pen max(g(X) - Y, 0)
+ *              with g the terminal condition on the row's own X (the same g_kind, strike,
+ *              g_alpha and g_cols), d phi / d Y = phi_r + pen 1[g(X) > Y] (strict: 0 at a
+ *              tie) and d phi / d Z unchanged.  pen == 0 is the problem without the field,
+ *              bit for bit.  pen != 0 is taken for kind DIAG only (with or without
+ *              dbsde_set_corr, any g_kind, q3 allowed); DBSDE_EINVAL from dbsde_create,
+ *              before any HIP call and with a message naming pen, for pen < 0, NaN or
+ *              infinite, pen != 0 on a Heston, Asian or geometric-Asian kind, and pen != 0
+ *              with u_clamp.  dbsde_pde_residual's phi and residual are the penalised
+ *              PDE's; dbsde_mc_value refuses pen != 0 (the problem is not linear: its
+ *              arbiter is DBSDE_EXACT_AMERICAN_PUT).  The last member: a caller filling
+ *              the 17 members before it and zeroing the struct keeps today's problem.
+ *              That holds at the source level only.  dbsde_config embeds dbsde_problem
+ *              by value, so the member moved T and device by four bytes while
+ *              DBSDE_ABI_VERSION stayed 3: a binary compiled against the header without
+ *              pen passes a shifted T with no version signal and must be recompiled.
  */
 typedef struct dbsde_problem {
   int kind;
@@ -183,6 +201,7 @@ typedef struct dbsde_problem {
   float g_alpha;
   int u_clamp;
   float h_kappa, h_theta, h_sigma, h_rho;
+  float pen;
 } dbsde_problem;
 
 typedef struct dbsde_config {
@@ -537,8 +556,31 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
  *                            delta [R, D]: d/dG = +-e^{-r tau} e^{M + V/2} N(+-d1) / G,
  *                            d/dS_i = that G tau / (k T S_i).  Needs sigma, K, G, S > 0.
  *                            (Kind 9 is not a closed form: DBSDE_EINVAL.)
+ *   DBSDE_EXACT_AMERICAN_PUT (14; kinds 12 and 13 are DBSDE_EINVAL)
+ *                            the put max(K - s, 0) with early exercise, by a
+ *                            Cox-Ross-Rubinstein tree in fp64: every coordinate of x [R, D]
+ *                            is priced on its own, ncol = D (price and delta [R * D]), params
+ *                            = {r, sigma, K, b, n_tree, pen}: b the risk-neutral drift of the
+ *                            asset (mu_a + phi_r phi_c of a dbsde_problem), n_tree an
+ *                            integer in [2, 4096], pen >= 0 or +inf.  With Delta = tau /
+ *                            n_tree, u = e^{sigma sqrt(Delta)}, d = 1 / u, p = (e^{b Delta} -
+ *                            d) / (u - d), node (i, j) at s u^{2j - i}, level n_tree holds
+ *                            g = max(K - s, 0) and below it c = e^{-r Delta} (p v_up + (1 - p)
+ *                            v_dn),
+ *                              pen = +inf:  v = max(c, g)                    the American value
+ *                              pen finite:  v = g > c ? (c + pen Delta g) / (1 + pen Delta) : c
+ *                            the value of the penalised problem a context with that pen
+ *                            trains on (pen = 0: the European tree).  delta = (v_11 - v_10) /
+ *                            (s u - s d), the level-1 difference quotient.  One workgroup
+ *                            per (point, coordinate), the level in LDS as doubles, barriers
+ *                            between a level's reads and writes, no atomics: bitwise
+ *                            repeatable.  DBSDE_EINVAL also for sigma or K <= 0, pen < 0 or
+ *                            NaN, n_tree outside [2, 4096] or not an integer.  p depends
+ *                            on the point's tau, which the host does not read: a point
+ *                            whose p is not in [0, 1] (a coarse tree, |b| sqrt(Delta) >
+ *                            sigma) has no tree value and gets NaN in price and delta.
  * t [R], x [R, D] device fp32; price [R * ncol] and delta (nullable),
- * ncol = D for BS_CALL / BS_PUT, 1 otherwise (GEO_ASIAN: price [R], delta [R, D]).  At t >= T the payoff and its
+ * ncol = D for BS_CALL / BS_PUT / AMERICAN_PUT, 1 otherwise (GEO_ASIAN: price [R], delta [R, D]).  At t >= T the payoff and its
  * 0 / 1/2 / 1 (put: 0 / -1/2 / -1) delta are returned, as the references do.
  * Computed in fp64.  DBSDE_EINVAL before any HIP call: an unknown kind; NULL t /
  * x / params / price; R or D < 1; a Heston kind with D != 2; a GEO_ASIAN kind with D < 2; t, x, price or
@@ -556,6 +598,7 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
 #define DBSDE_EXACT_HESTON_PUT 8
 #define DBSDE_EXACT_GEO_ASIAN 10
 #define DBSDE_EXACT_GEO_ASIAN_PUT 11
+#define DBSDE_EXACT_AMERICAN_PUT 14
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* hip_stream);
 
@@ -642,7 +685,8 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * DBSDE_EINVAL before any HIP call: NULL prob / t / x / value; P, D, n_steps
  * or mc < 1; mc > 2^32; D > 4096; Heston with an odd D, with L or with delta;
  * L with D > 128; HESTON_CORR without L, with an odd D, with delta or with
- * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0; ASIAN with D < 2,
+ * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0; pen != 0 (not linear:
+ * the arbiter of a penalised problem is DBSDE_EXACT_AMERICAN_PUT); ASIAN with D < 2,
  * phi_c != 0, g_cols != 1, g_kind SUMSQ or LOG, or L with D - 1 > 128; GEO_ASIAN with any
  * of those or sig_b != 0.  Needs no context;
  * the work is enqueued on hip_stream.

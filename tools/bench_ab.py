@@ -5,7 +5,10 @@ profiles/heston_corr_bench_ab.json have this format).  Needs a GPU.
     python tools/bench_ab.py PARENT_LIB OUT.json [PARENT_COMMIT] [REPEATS] [WORKLOADS]
 
 PARENT_LIB is a libdbsde.so built from the parent commit; each run selects its
-library through DBSDE_LIB (the in-tree one when unset).  Per workload (WORKLOADS,
+library through DBSDE_LIB (the in-tree one when unset).  When a change alters a
+struct of the C ABI (dbsde_problem gained a member), this tree's binding cannot
+drive the parent's library: PARENT_LIB is then a directory, a built checkout of
+the parent commit, and the parent arm runs that checkout's own bench.py.  Per workload (WORKLOADS,
 comma-separated names of bench.py's --workload; default bsb,heston): `python
 bench.py --gpus 1 --steps 50 --warmup 10`, parent and this change alternating
 REPEATS (5) times, the order inside each pair alternating too; then
@@ -29,14 +32,17 @@ DUMPS = os.path.join(ROOT, "bench_out", "bench_ab")
 def bench(arm, workload, dump=None):
     env = dict(os.environ)
     env.pop("DBSDE_LIB", None)
-    if arm == "parent":
+    root = ROOT
+    if arm == "parent" and os.path.isdir(PARENT_LIB):
+        root = PARENT_LIB
+    elif arm == "parent":
         env["DBSDE_LIB"] = PARENT_LIB
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10"]
     if workload != "bsb":
         cmd += ["--workload", workload]
     if dump:
         cmd += ["--dump-outputs", dump]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
         sys.exit(f"bench.py failed on the {arm} library (exit {r.returncode}); nothing further is started")
