@@ -13,7 +13,8 @@ Import it with importlib (the directory name is not a Python identifier):
 from . import _lib
 from .deepbsde import BlackScholesBarenblatt, u_exact
 from .fbsnn import FBSNN, PredictionGenerator
-from .problems import (AmericanBasketPutOption, AmericanPutOption, AsianBasketCallOption, AsianBasketPutOption, AsianCallOption, AsianPutOption,
+from .problems import (AmericanBasketPutOption, AmericanPutOption, BarrierBasketCallOption, BarrierBasketPutOption,
+                       BarrierCallOption, BarrierPutOption, AsianBasketCallOption, AsianBasketPutOption, AsianCallOption, AsianPutOption,
                        BasketCallOption, BasketPutOption, BSPDETestCase, CallOption, CallOption1D,
                        GeometricAsianBasketCallOption, GeometricAsianBasketPutOption, GeometricAsianCallOption,
                        GeometricAsianPutOption, HamiltonJacobiBellman, HestonFBSNN, HestonTwoFactorFBSNN, PutOption)
@@ -25,4 +26,5 @@ __all__ = ["FBSNN", "PredictionGenerator", "BlackScholesBarenblatt", "u_exact", 
            "AsianCallOption", "AsianPutOption", "AsianBasketCallOption", "AsianBasketPutOption",
            "GeometricAsianCallOption", "GeometricAsianPutOption", "GeometricAsianBasketCallOption",
            "GeometricAsianBasketPutOption", "AmericanPutOption", "AmericanBasketPutOption",
+           "BarrierCallOption", "BarrierPutOption", "BarrierBasketCallOption", "BarrierBasketPutOption",
            "NativeSolver", "ProblemSpec", "exact", "free_call_profile", "hjb_mc", "mc_value", "_lib"]

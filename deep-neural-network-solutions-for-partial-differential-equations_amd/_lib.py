@@ -22,11 +22,13 @@ PROBLEM_KINDS = {"diag": 0, "heston": 1, "heston2": 2}
 PROB_HESTON_CORR = 3   # dbsde_mc_value's kind for "heston" with a factor between the assets: not a context kind
 PROB_ASIAN = 4         # ProblemSpec(kind="diag", average=True): state [A, S_1..S_k], A the running average
 PROB_GEO_ASIAN = 8     # ProblemSpec(kind="diag", average="geometric"): state [G, S_1..S_k], G the geometric average
+PROB_BARRIER = 11      # ProblemSpec(kind="diag", barrier=B): the diag process knocked out at B (sent in h_kappa)
 OPTIMIZERS = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3, "Adagrad": 4, "Adamax": 5, "Adadelta": 6, "ASGD": 7}
 EXACT_KINDS = {"bsb": 0, "bs_call": 1, "basket_avg": 2, "basket_mean": 3, "heston": 4,
                "bs_put": 5, "basket_avg_put": 6, "basket_mean_put": 7, "heston_put": 8,
                "geo_asian": 10, "geo_asian_put": 11,   # (9 is no closed form; 12 and 13 are unknown)
-               "american_put": 14}                     # a binomial tree, not a closed form
+               "american_put": 14,                     # a binomial tree, not a closed form
+               "barrier_call": 15, "barrier_put": 16}  # down-and-out call, up-and-out put (one asset)
 ABI_VERSION = 3
 
 # every symbol include/dbsde.h declares (checked by the CPU test suite)

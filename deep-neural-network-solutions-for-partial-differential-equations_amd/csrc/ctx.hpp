@@ -53,6 +53,30 @@ inline const char* geo_asian_refusal(const dbsde_problem& pr, int D) {
   if (pr.sig_b != 0.f) return "the geometric-average problem needs sig_b == 0 (log S needs positive assets)";
   return nullptr;
 }
+// DBSDE_PROB_BARRIER (DIAG's state, h_kappa the barrier level B): why
+// dbsde_create and dbsde_mc_value refuse the problem, or null.  Only the regular
+// barriers (B on the payoff's zero side of the strike), so g and its gradient
+// vanish on a knocked state.
+inline const char* barrier_refusal(const dbsde_problem& pr) {
+  const float B = pr.h_kappa;
+  if (!(B > 0.f) || std::isinf(B)) return "h_kappa (the barrier level B of kind BARRIER) must be finite and > 0";
+  if (pr.g_kind != DBSDE_G_CALL_SUM && pr.g_kind != DBSDE_G_CALL_MEAN && pr.g_kind != DBSDE_G_PUT_SUM &&
+      pr.g_kind != DBSDE_G_PUT_MEAN)
+    return "g_kind: the barrier problem takes call_sum, call_mean, put_sum and put_mean only (its payoff must vanish "
+           "beyond the barrier)";
+  const bool put = pr.g_kind >= DBSDE_G_PUT_SUM;
+  if (!put && B > pr.strike)
+    return "h_kappa (the barrier B) must be <= strike for a down-and-out call (reverse barriers need an indicator payoff)";
+  if (put && B < pr.strike)
+    return "h_kappa (the barrier B) must be >= strike for an up-and-out put (reverse barriers need an indicator payoff)";
+  if (pr.pen != 0.f) return "pen != 0 cannot be combined with the barrier problem";
+  if (pr.q3) return "q3 cannot be combined with the barrier problem";
+  if (pr.u_clamp) return "u_clamp cannot be combined with the barrier problem";
+  if (pr.h_theta != 0.f) return "h_theta must be 0 for the barrier problem (only h_kappa is used: the barrier level)";
+  if (pr.h_sigma != 0.f) return "h_sigma must be 0 for the barrier problem (only h_kappa is used: the barrier level)";
+  if (pr.h_rho != 0.f) return "h_rho must be 0 for the barrier problem (only h_kappa is used: the barrier level)";
+  return nullptr;
+}
 // dbsde_problem.pen (the penalised American driver): why dbsde_create refuses
 // the problem, or null
 inline const char* pen_refusal(const dbsde_problem& pr) {
@@ -157,6 +181,7 @@ struct dbsde_ctx {
   int nb = 0;                 // Brownian dimension (D; D/2 for Heston, kind 1; D - 1 for Asian, kinds 4 and 8)
   bool asian = false;         // DBSDE_PROB_ASIAN: state [A, S_1..S_k], A the running average (nb = D - 1)
   bool geo = false;           // DBSDE_PROB_GEO_ASIAN: asian is set too, column 0 is the geometric average G
+  bool barrier = false;       // DBSDE_PROB_BARRIER: DIAG's rollouts, then the stop pass (problem.h_kappa = B)
   int gcols = 0;              // state columns entering g and the terminal Z loss
   bool heston = false, u_clamp = false;
   bool heston2 = false;       // DBSDE_PROB_HESTON2: two Brownian motions per asset (nb = D)

@@ -151,6 +151,46 @@ __global__ void __launch_bounds__(256) geo_asian_exact_kernel(ExactArgs a) {
   }
 }
 
+// DBSDE_EXACT_BARRIER_CALL / _PUT: the down-and-out call (B <= K) and the up-and-out
+// put (B >= K) without rebate on one GBM asset with cost of carry b (Reiner and
+// Rubinstein 1991; include/dbsde.h has the terms): A - C, f = +1 / -1.  n_mon > 0
+// first moves B away from S by exp(-+0.5826 sigma sqrt(tau / n_mon)) (Broadie,
+// Glasserman and Kou 1997), the continuity correction for n_mon monitoring dates.
+// The S-derivatives of the normal densities cancel inside A and inside C (S e^{(b - r)
+// tau} n(x1) = K e^{-r tau} n(x1 - s), and the same with the (B / S) powers at y1), so
+//   delta = f e^{(b - r) tau} N(f x1) + f e^{(b - r) tau} (2 lambda + 1) (B / S)^{2 lambda + 2} N(f y1)
+//           - 2 lambda f K e^{-r tau} (B / S)^{2 lambda} N(f y1 - f s) / S.
+// Thread per (point, coordinate); p = {r, sigma, K, b, B, n_mon}.
+template <bool PUT>
+__global__ void __launch_bounds__(256) barrier_exact_kernel(ExactArgs a) {
+  const long long i = blockIdx.x * 256LL + threadIdx.x;
+  if (i >= a.R * a.D) return;
+  const double tau = a.T - (double)a.t[i / a.D];
+  const double S = (double)a.x[i];
+  const double r = a.p0, sig = a.p1, K = a.p2, b = a.p3, nm = a.p5;
+  const double f = PUT ? -1.0 : 1.0;
+  double B = a.p4, price = 0.0, delta = 0.0;
+  if (tau > 0.0) {
+    if (nm > 0.0) B *= exp(-f * 0.5826 * sig * sqrt(tau / nm));
+    if (PUT ? S < B : S > B) {
+      const double s = sig * sqrt(tau), lam = (b - 0.5 * sig * sig) / (sig * sig);
+      const double x1 = log(S / K) / s + (1.0 + lam) * s;
+      const double y1 = log(B * B / (S * K)) / s + (1.0 + lam) * s;
+      const double cf = exp((b - r) * tau), df = exp(-r * tau);
+      const double pw0 = pow(B / S, 2.0 * lam), pw1 = pw0 * (B / S) * (B / S);
+      const double Nx1 = ncdf(f * x1), Nx2 = ncdf(f * (x1 - s)), Ny1 = ncdf(f * y1), Ny2 = ncdf(f * (y1 - s));
+      const double A = f * S * cf * Nx1 - f * K * df * Nx2;
+      const double C = f * S * cf * pw1 * Ny1 - f * K * df * pw0 * Ny2;
+      price = A - C;
+      delta = f * cf * Nx1 + f * cf * (2.0 * lam + 1.0) * pw1 * Ny1 - 2.0 * lam * f * K * df * pw0 * Ny2 / S;
+    }
+  } else if (PUT ? S < B : S > B) {
+    bs_price<PUT>(S, K, tau, r, sig, price, delta);   // the payoff and its kink delta
+  }
+  a.price[i] = (float)price;
+  if (a.delta) a.delta[i] = (float)delta;
+}
+
 // --------------------------------------------------------------------------
 // DBSDE_EXACT_AMERICAN_PUT: the put with early exercise on a Cox-Ross-Rubinstein
 // tree in fp64 (include/dbsde.h): the arbiter of the penalised
@@ -471,7 +511,8 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
                 float* price, float* delta, void* stream) {
   const bool geo = kind == DBSDE_EXACT_GEO_ASIAN || kind == DBSDE_EXACT_GEO_ASIAN_PUT;
   const bool tree = kind == DBSDE_EXACT_AMERICAN_PUT;
-  if (kind < DBSDE_EXACT_BSB || (kind > DBSDE_EXACT_HESTON_PUT && !geo && !tree) || !t || !x || !params || !price ||
+  const bool bar = kind == DBSDE_EXACT_BARRIER_CALL || kind == DBSDE_EXACT_BARRIER_PUT;
+  if (kind < DBSDE_EXACT_BSB || (kind > DBSDE_EXACT_HESTON_PUT && !geo && !tree && !bar) || !t || !x || !params || !price ||
       R < 1 || D < 1)
     return DBSDE_EINVAL;
   if (geo && D < 2) return DBSDE_EINVAL;   // x = [G, S_1..S_k]
@@ -506,6 +547,39 @@ int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, fl
     g.price = price;
     g.delta = delta;
     american_put_tree_kernel<<<(unsigned)(R * D), TREE_THREADS, 0, (hipStream_t)stream>>>(g);
+    return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
+  }
+  if (bar) {   // params = {r, sigma, K, b, B, n_mon}; price and delta [R, D]
+    const bool put = kind == DBSDE_EXACT_BARRIER_PUT;
+    auto bad = [](const std::string& m) { return fail(nullptr, DBSDE_EINVAL, "dbsde_exact(DBSDE_EXACT_BARRIER_*): " + m); };
+    if (!std::isfinite(params[0]) || !std::isfinite(params[3])) return bad("r and b must be finite");
+    if (!(params[1] > 0.0) || !std::isfinite(params[1])) return bad("sigma must be > 0");
+    if (!(params[2] > 0.0) || !std::isfinite(params[2])) return bad("K must be > 0");
+    if (!(params[4] > 0.0) || !std::isfinite(params[4])) return bad("B must be > 0");
+    if (!put && params[4] > params[2]) return bad("the down-and-out call needs B <= K");
+    if (put && params[4] < params[2]) return bad("the up-and-out put needs B >= K");
+    if (!(params[5] >= 0.0) || !std::isfinite(params[5])) return bad("n_mon must be >= 0 (0: continuous monitoring)");
+    if (R > 0x7fffffffLL * 256 / D) return bad("R * D is too large for one launch");
+    ExactArgs g{};
+    g.kind = kind;
+    g.D = D;
+    g.R = R;
+    g.T = T;
+    g.p0 = params[0];
+    g.p1 = params[1];
+    g.p2 = params[2];
+    g.p3 = params[3];
+    g.p4 = params[4];
+    g.p5 = params[5];
+    g.t = t;
+    g.x = x;
+    g.price = price;
+    g.delta = delta;
+    const unsigned nblk = (unsigned)((R * D + 255) / 256);
+    if (put)
+      barrier_exact_kernel<true><<<nblk, 256, 0, (hipStream_t)stream>>>(g);
+    else
+      barrier_exact_kernel<false><<<nblk, 256, 0, (hipStream_t)stream>>>(g);
     return hipGetLastError() == hipSuccess ? DBSDE_OK : DBSDE_EHIP;
   }
   if (geo) {   // params = {mu, r, sigma, K, cbar, vbar}; delta [R, D]

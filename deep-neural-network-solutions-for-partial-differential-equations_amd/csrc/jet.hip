@@ -336,6 +336,8 @@ struct PdeArgs {
   dbsde_problem pr;
   int heston, D, nb, nd;   // heston: 0 DIAG, 1 HESTON, 2 HESTON2
   float rhob;              // HESTON2: fp32(sqrt(1 - (double)h_rho^2))
+  // (DBSDE_PROB_BARRIER has heston = asian = 0: DIAG's drift and diffusion columns.  The generators of the stopped
+  // and the unstopped process agree on the live side of the barrier; the residual means nothing beyond it.)
   int asian;               // 1 DBSDE_PROB_ASIAN: state [A, S_1..S_nb] (heston = 0); 2 DBSDE_PROB_GEO_ASIAN: [G, S]
   float T;                 // its averaging horizon
   int gcols;               // leading state columns entering g (pr.pen != 0: the penalty's g)

@@ -32,6 +32,24 @@
 // Delta: dG_T/dG_p = G_T / G_p, dG_T/dS_d = G_T (sum_n (double)fp32((J_{d,n} /
 // S_{d,n}) dt_n)) / (k T).
 //
+// Knock-out (DBSDE_PROB_BARRIER, mc_barrier_kernel): the summand is g(X_N) times
+// alive = no row 0..n_steps of the sample's path was knocked.  The statistic needs a
+// sum over the assets at every step, which the thread-per-(sample, coordinate) layout
+// above does not have, so the kind has a kernel of its own: a 16-lane group runs one
+// sample of one point, lane l the assets l, l + 16, .. (nd <= 128: eight per lane, in
+// registers), and per step the lanes form barrier_stat's sum -- their ascending fp32
+// partial sums met in the xor butterfly, asian_row_sum's order exactly -- and compare
+// in fp32 (barrier_hit).  A knocked sample stops there (its summand is 0).  g(X_N)
+// takes the fp64 sum of the lanes' ascending fp64 partial sums met in the same
+// butterfly.  Workgroup = 16 groups = 16 samples side by side; grid (point, chunk);
+// each group accumulates sum g and sum g^2 over its samples in fp64, the 16 groups
+// are summed in order into the partials and mc_barrier_final_kernel sums the chunks:
+// no atomics, bitwise repeatable, and a point's result depends on neither P nor its
+// index (a workgroup serves one point; the chunking is a function of mc alone).  With
+// L the unscaled L z come from the correlated Heston's increment workspace (below),
+// with its bound and grouping.  No delta: the pathwise estimator is biased across
+// the indicator.
+//
 // Draws.  The normals of sample k, step n, Brownian coordinate d are
 // philox_normal4(seed, offset, k, n >> 2, d)[n & 3] -- the device-mode rollout's
 // keying for global path k -- for EVERY point of a call (common random numbers).
@@ -141,6 +159,9 @@ struct McArgs {
   const float* ws;                 // the group's unscaled increments L z [samples, n_steps, nd]
   long long ws_k0;                 // its first sample
   int ch0;                         // its first chunk: workgroup row blockIdx.y runs chunk ch0 + blockIdx.y
+  // knock-out (mc_barrier_kernel): barrier_hit's B and gsign, barrier_stat's mean
+  float bar_B, bar_gsign;
+  int bar_mean;
 };
 
 __device__ __forceinline__ int mc_lp_off(int j, int nd) { return j * nd - (j * (j - 1)) / 2; }
@@ -515,6 +536,144 @@ __global__ void __launch_bounds__(256) mc_final_kernel(McArgs a, float* value, f
   }
 }
 
+// --------------------------------------------------------------------------
+// Knock-out problems (the header comment has the layout)
+// --------------------------------------------------------------------------
+constexpr int MB_GROUPS = MC_THREADS / ASIAN_LANES;   // samples side by side in a workgroup
+constexpr int MB_AMAX = MC_NBMAX / ASIAN_LANES;       // assets per lane
+
+// barrier_stat over the lane's columns X[j] = coordinate l + 16 j (the columns below
+// cols): asian_lane_sum's ascending partial, then the butterfly
+__device__ __forceinline__ float mb_stat(const float (&X)[MB_AMAX], int l, int cols, bool mean) {
+  float p = 0.f;
+#pragma unroll
+  for (int j = 0; j < MB_AMAX; ++j)
+    if (l + ASIAN_LANES * j < cols) p = rn_add(p, X[j]);
+#pragma unroll
+  for (int o = 1; o < ASIAN_LANES; o <<= 1) p = rn_add(p, __shfl_xor(p, o));
+  return mean ? asian_mean(p, cols) : p;
+}
+
+template <bool WS>
+__global__ void __launch_bounds__(MC_THREADS) mc_barrier_kernel(McArgs a) {
+  __shared__ double red[2][MB_GROUPS];
+  const int tid = threadIdx.x, grp = tid / ASIAN_LANES, l = tid & (ASIAN_LANES - 1);
+  const int p = blockIdx.x, nd = a.nd;
+  int ch = blockIdx.y;
+  if constexpr (WS) ch += a.ch0;
+  const float sq = a.sqdt[p];
+  const bool mean = a.bar_mean != 0;
+  float x0[MB_AMAX];
+#pragma unroll
+  for (int j = 0; j < MB_AMAX; ++j) x0[j] = l + ASIAN_LANES * j < nd ? a.x[(size_t)p * a.D + l + ASIAN_LANES * j] : 0.f;
+  const long long k0 = (long long)ch * a.per, k1 = k0 + a.per < a.mc ? k0 + a.per : a.mc;
+  double gs = 0.0, g2 = 0.0;
+  for (long long kb = k0; kb < k1; kb += MB_GROUPS) {
+    const long long kk = kb + grp;
+    if (kk >= k1) continue;   // (the group's 16 lanes agree)
+    float X[MB_AMAX];
+#pragma unroll
+    for (int j = 0; j < MB_AMAX; ++j) X[j] = x0[j];
+    bool alive = !barrier_hit(mb_stat(X, l, a.gcols, mean), a.bar_B, a.bar_gsign);   // row 0 counts
+    for (int n0 = 0; n0 < a.n_steps && alive; n0 += 4) {
+      float z[MB_AMAX][4];
+#pragma unroll
+      for (int j = 0; j < MB_AMAX; ++j) {
+        const int d = l + ASIAN_LANES * j;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) z[j][i] = 0.f;
+        if (d >= nd) continue;
+        if constexpr (WS) {
+          const float* wz = a.ws + (size_t)(kk - a.ws_k0) * a.n_steps * nd + d;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (n0 + i < a.n_steps) z[j][i] = wz[(size_t)(n0 + i) * nd];
+        } else {
+          philox_normal4(a.seed, a.offset, (uint32_t)kk, (uint32_t)(n0 >> 2), (uint32_t)d, z[j]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (n0 + i >= a.n_steps || !alive) break;
+        const float dt = a.dtab[(size_t)(n0 + i) * a.Ppad + p];
+#pragma unroll
+        for (int j = 0; j < MB_AMAX; ++j)
+          if (l + ASIAN_LANES * j < nd) diag_step(a.mu, a.sig_a, a.sig_b, dt, rn_mul(sq, z[j][i]), X[j]);
+        alive = !barrier_hit(mb_stat(X, l, a.gcols, mean), a.bar_B, a.bar_gsign);
+      }
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < MB_AMAX; ++j)
+      if (l + ASIAN_LANES * j < a.gcols) sum += (double)X[j];
+#pragma unroll
+    for (int o = 1; o < ASIAN_LANES; o <<= 1) sum += __shfl_xor(sum, o);
+    double g, gp;
+    mc_payoff(a.g_kind, sum, (double)a.gcols, (double)a.strike, (double)a.g_alpha, g, gp);
+    if (!alive) g = 0.0;
+    gs += g;
+    g2 += g * g;
+  }
+  if (l == 0) {
+    red[0][grp] = gs;
+    red[1][grp] = g2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int r = 0; r < MB_GROUPS; ++r) {
+      s1 += red[0][r];
+      s2 += red[1][r];
+    }
+    double* q = a.part + ((size_t)p * a.nch + ch) * a.W;
+    q[0] = s1;
+    q[1] = s2;
+  }
+}
+
+// value and standard error of point p (blockIdx.x) from the chunk partials, as
+// mc_final_kernel forms them; a point at maturity gets g(x_p) and 0, or 0 and 0
+// when x_p is beyond the barrier.  One wave per point: its first 16 lanes form
+// barrier_stat, and g's fp64 sum runs in mc_barrier_kernel's order.
+__global__ void __launch_bounds__(64) mc_barrier_final_kernel(McArgs a, float* value, float* stderr_) {
+  const int p = blockIdx.x, l = threadIdx.x & (ASIAN_LANES - 1);
+  const float tau = rn_sub(a.T, a.t[p]);
+  const float* xp = a.x + (size_t)p * a.D;
+  if (!(tau > 0.f)) {
+    float X[MB_AMAX];
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < MB_AMAX; ++j) {
+      X[j] = l + ASIAN_LANES * j < a.nd ? xp[l + ASIAN_LANES * j] : 0.f;
+      if (l + ASIAN_LANES * j < a.gcols) sum += (double)X[j];
+    }
+    const bool hit = barrier_hit(mb_stat(X, l, a.gcols, a.bar_mean != 0), a.bar_B, a.bar_gsign);
+#pragma unroll
+    for (int o = 1; o < ASIAN_LANES; o <<= 1) sum += __shfl_xor(sum, o);
+    double g, gp;
+    mc_payoff(a.g_kind, sum, (double)a.gcols, (double)a.strike, (double)a.g_alpha, g, gp);
+    if (threadIdx.x == 0) {
+      value[p] = hit ? 0.f : (float)g;
+      if (stderr_) stderr_[p] = 0.f;
+    }
+    return;
+  }
+  if (threadIdx.x != 0) return;
+  const double disc = exp(-(double)a.phi_r * (double)tau), n = (double)a.mc;
+  const double* q = a.part + (size_t)p * a.nch * a.W;
+  double s1 = 0.0, s2 = 0.0;
+  for (int h = 0; h < a.nch; ++h) {
+    s1 += q[(size_t)h * a.W];
+    s2 += q[(size_t)h * a.W + 1];
+  }
+  value[p] = (float)(disc * (s1 / n));
+  if (stderr_) {
+    double var = a.mc > 1 ? (s2 - s1 * s1 / n) / (n - 1.0) : 0.0;
+    if (!(var > 0.0)) var = 0.0;
+    stderr_[p] = (float)(disc * sqrt(var / n));
+  }
+}
+
 }  // namespace dbsde
 
 using namespace dbsde;
@@ -532,7 +691,8 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   if (mc > (1LL << 32)) return bad("mc must be <= 2^32 (the sample index is a 32-bit counter word)");
   if (D > MC_DMAX) return bad("D must be <= 4096");
   if (prob->kind != DBSDE_PROB_DIAG && prob->kind != DBSDE_PROB_HESTON && prob->kind != DBSDE_PROB_HESTON2 &&
-      prob->kind != DBSDE_PROB_HESTON_CORR && prob->kind != DBSDE_PROB_ASIAN && prob->kind != DBSDE_PROB_GEO_ASIAN)
+      prob->kind != DBSDE_PROB_HESTON_CORR && prob->kind != DBSDE_PROB_ASIAN && prob->kind != DBSDE_PROB_GEO_ASIAN &&
+      prob->kind != DBSDE_PROB_BARRIER)
     return bad("unknown problem kind");
   if (prob->g_kind < DBSDE_G_SUMSQ || prob->g_kind > DBSDE_G_SMOOTH_PUT) return bad("unknown terminal condition g_kind");
   if (prob->phi_zz != 0.f)
@@ -560,6 +720,17 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
     if (L && D - 1 > MC_NBMAX) return bad("L needs D - 1 <= 128 assets");
   }
   if (!hcorr && !asian && L && D > MC_NBMAX) return bad("L needs D <= 128");
+  // knock-out: DIAG's state and step, a kernel of its own (a 16-lane group per sample)
+  const bool barrier = prob->kind == DBSDE_PROB_BARRIER;
+  if (barrier) {
+    if (const char* why = barrier_refusal(*prob)) return bad(why);
+    if (D > MC_NBMAX) return bad("the barrier problem needs D <= 128 (a 16-lane group holds a sample's assets)");
+    if (delta)
+      return bad("no pathwise delta for the barrier problem (the estimator is biased across the knock-out "
+                 "indicator); bump and reprice on the same draws");
+    if (L && (n_steps + 3) / 4 > 65535) return bad("the barrier problem with L needs n_steps <= 262140");
+  }
+  const bool wsinc = hcorr || (barrier && L);   // increments from the workspace the increment GEMM fills
 
   McArgs a{};
   a.D = D;
@@ -570,6 +741,7 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   a.n_steps = n_steps;
   a.nj = a.nd > MC_THREADS ? (a.nd + MC_THREADS - 1) / MC_THREADS : 1;
   a.S = a.nj > 1 ? 1 : (MC_THREADS / a.nd < MC_SMAX ? MC_THREADS / a.nd : MC_SMAX);
+  if (barrier) a.S = MB_GROUPS;   // a function of nothing: the chunking depends on mc alone
   const long long per0 = (mc + MC_CHUNKS - 1) / MC_CHUNKS;
   a.per = (per0 + a.S - 1) / a.S * a.S;
   a.nch = (int)((mc + a.per - 1) / a.per);
@@ -596,16 +768,19 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   a.t = t;
   a.x = x;
   a.L = L;
+  a.bar_B = prob->h_kappa;
+  a.bar_gsign = prob->g_kind >= DBSDE_G_PUT_SUM ? -1.f : 1.f;
+  a.bar_mean = prob->g_kind == DBSDE_G_CALL_MEAN || prob->g_kind == DBSDE_G_PUT_MEAN;
 
   hipStream_t st = (hipStream_t)stream;
   const size_t b_part = up256((size_t)P * a.nch * a.W * sizeof(double));
   const size_t b_dtab = up256((size_t)n_steps * a.Ppad * sizeof(float));
   const size_t b_sq = up256((size_t)a.Ppad * sizeof(float));
-  const size_t b_lp = hcorr ? up256((size_t)a.nd * a.nd * sizeof(float)) : L ? up256((size_t)MC_LPACK * sizeof(float)) : 0;
-  // correlated Heston: the chunks of a group and its workspace
+  const size_t b_lp = wsinc ? up256((size_t)a.nd * a.nd * sizeof(float)) : L ? up256((size_t)MC_LPACK * sizeof(float)) : 0;
+  // correlated Heston (and the knock-out kind with L): the chunks of a group and its workspace
   int cg = a.nch;
   size_t b_ws = 0;
-  if (hcorr) {
+  if (wsinc) {
     const char* e = getenv("DBSDE_MC_WS_MB");
     const double mb = e ? atof(e) : 0.0;   // megabytes, fractions allowed; unset or not positive: the default
     const double chunk = (double)a.per * n_steps * a.nd * sizeof(float);
@@ -620,12 +795,12 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
   a.part = (double*)buf;
   a.dtab = (float*)(buf + b_part);
   a.sqdt = (float*)(buf + b_part + b_dtab);
-  a.Lp = L && !hcorr ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
-  a.Lt = hcorr ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
+  a.Lp = L && !wsinc ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
+  a.Lt = wsinc ? (float*)(buf + b_part + b_dtab + b_sq) : nullptr;
 
   mc_grid_kernel<<<(a.Ppad + 255) / 256, 256, 0, st>>>(a);
   const dim3 grid(tiles, a.nch);
-  if (hcorr) {
+  if (wsinc) {
     dbsde_ctx* pc = free_call_ctx();
     if (pc->prof) pc->stream = st;   // what dbsde_profile_read(NULL, ...) synchronises
     a.ws = (const float*)(buf + b_part + b_dtab + b_sq + b_lp);
@@ -636,7 +811,11 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
       a.ws_k0 = (long long)c0 * a.per;
       const long long count = std::min<long long>((long long)nc * a.per, mc - a.ws_k0);
       rc = mc_corr_increments(pc, st, a.Lt, a.nd, n_steps, seed, offset, a.ws_k0, count, (float*)a.ws);
-      if (rc == DBSDE_OK)
+      if (rc == DBSDE_OK && barrier)
+        rc = run(pc, st, "mc_barrier_paths", 0.0, 4.0 * (double)count * n_steps * a.nd * P, [&]() {
+          mc_barrier_kernel<true><<<dim3(P, nc), MC_THREADS, 0, st>>>(a);
+        });
+      else if (rc == DBSDE_OK)
         rc = run(pc, st, "mc_heston_corr_paths", 0.0, 4.0 * (double)count * n_steps * a.nd * tiles, [&]() {
           mc_kernel<MC_HESTON, false, true><<<dim3(tiles, nc), MC_THREADS, 0, st>>>(a);
         });
@@ -645,7 +824,9 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
       (void)hipFreeAsync(buf, st);
       return rc;
     }
-  } else if (heston2)
+  } else if (barrier)
+    mc_barrier_kernel<false><<<dim3(P, a.nch), MC_THREADS, 0, st>>>(a);
+  else if (heston2)
     mc_kernel<MC_HESTON2, false><<<grid, MC_THREADS, 0, st>>>(a);
   else if (heston)
     mc_kernel<MC_HESTON, false><<<grid, MC_THREADS, 0, st>>>(a);
@@ -673,7 +854,10 @@ extern "C" int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const f
     mc_kernel<MC_DIAG, true><<<grid, MC_THREADS, 0, st>>>(a);
   else
     mc_kernel<MC_DIAG, false><<<grid, MC_THREADS, 0, st>>>(a);
-  mc_final_kernel<<<dim3(P, ((delta ? D : 0) + 256) / 256), 256, 0, st>>>(a, value, stderr_, delta);
+  if (barrier)
+    mc_barrier_final_kernel<<<P, 64, 0, st>>>(a, value, stderr_);
+  else
+    mc_final_kernel<<<dim3(P, ((delta ? D : 0) + 256) / 256), 256, 0, st>>>(a, value, stderr_, delta);
   const hipError_t e = hipGetLastError();
   (void)hipFreeAsync(buf, st);
   if (e != hipSuccess) return fail(nullptr, DBSDE_EHIP, std::string("dbsde_mc_value: ") + hipGetErrorString(e));

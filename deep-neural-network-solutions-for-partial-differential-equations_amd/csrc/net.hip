@@ -282,7 +282,7 @@ int build_net(dbsde_ctx* c) {
                 "DBSDE_PROB_HESTON_CORR is dbsde_mc_value's kind: a context takes kind DBSDE_PROB_HESTON plus "
                 "dbsde_set_corr");
   if (pr.kind != DBSDE_PROB_DIAG && pr.kind != DBSDE_PROB_HESTON && pr.kind != DBSDE_PROB_HESTON2 &&
-      pr.kind != DBSDE_PROB_ASIAN && pr.kind != DBSDE_PROB_GEO_ASIAN)
+      pr.kind != DBSDE_PROB_ASIAN && pr.kind != DBSDE_PROB_GEO_ASIAN && pr.kind != DBSDE_PROB_BARRIER)
     return fail(c, DBSDE_EINVAL, "unknown problem kind");
   if (pr.g_kind < 0 || pr.g_kind > DBSDE_G_SMOOTH_PUT) return fail(c, DBSDE_EINVAL, "unknown terminal condition");
   c->heston = pr.kind == DBSDE_PROB_HESTON;
@@ -293,6 +293,9 @@ int build_net(dbsde_ctx* c) {
     if (const char* why = c->geo ? geo_asian_refusal(pr, c->D) : asian_refusal(pr, c->D))
       return fail(c, DBSDE_EINVAL, why);
   }
+  c->barrier = pr.kind == DBSDE_PROB_BARRIER;   // DIAG's state, rollouts and coefficients, plus the stop pass
+  if (c->barrier)
+    if (const char* why = barrier_refusal(pr)) return fail(c, DBSDE_EINVAL, why);
   if (const char* why = pen_refusal(pr)) return fail(c, DBSDE_EINVAL, why);
   if ((c->heston || c->heston2) && c->D % 2 != 0)
     return fail(c, DBSDE_EINVAL, "Heston state is [S_1..S_k, v_1..v_k]: layers[0] - 1 must be even");

@@ -1061,6 +1061,76 @@ __global__ void __launch_bounds__(AA_THREADS) rollout_asian_avg_kernel(RolloutAr
   }
 }
 
+// --------------------------------------------------------------------------
+// Knock-out (barrier) problems (DBSDE_PROB_BARRIER): DIAG's rows from whichever
+// rollout form ran before (one pass, draw + chain, the correlated kernels, the
+// caller's t / W), then this pass stops each path at its first hit row
+// (barrier_stop, sde.hpp, restated over a 16-lane group per path as
+// rollout_asian_avg_kernel is).  Per row lane l sums the payoff's columns
+// 1 + l, 1 + l + 16, .. ascending and the lanes meet in the xor butterfly
+// (asian_row_sum's order), BS_ROWS rows' loads in flight before their
+// comparisons; every lane of the group ends with the same sum, so the lanes
+// agree on tau and leave the scan together.  Then the group's lanes own the
+// 16-byte column groups c = l, l + 16, ..: the state columns of rows n > tau
+// get row tau's, those of sdw rows tau .. N - 1 get 0 (row N is 0 already) --
+// whole float4 stores where all four columns are state columns, single floats
+// in the two edge groups, which hold t (column 0) and the constant 1 (column
+// D + 1): neither is touched.  A path that never hits, or hits at row N, writes
+// nothing.  Reads happen before the scan ends and writes only after it, to
+// rows the group no longer reads, and no other group touches the path.
+// --------------------------------------------------------------------------
+struct BarrierArgs {
+  float B, gsign;   // barrier_hit's: gsign > 0 knocks at stat <= B, gsign < 0 at stat >= B
+  int cols, mean;   // the payoff's g_cols columns; mean: stat = sum / cols
+};
+constexpr int BS_ROWS = 4;        // row sums in flight per scan block
+constexpr int BS_THREADS = 256;   // 16 paths per workgroup
+__global__ void __launch_bounds__(BS_THREADS) rollout_barrier_stop_kernel(RolloutArgs p, BarrierArgs b) {
+  const long long gid = (long long)blockIdx.x * BS_THREADS + threadIdx.x;
+  if (gid / ASIAN_LANES >= p.M) return;   // (a 16-lane group is one path: its lanes leave together)
+  const int m = (int)(gid / ASIAN_LANES), l = (int)(gid & (ASIAN_LANES - 1));
+  const int N1 = p.N + 1;
+  float* xr = p.xin + (size_t)m * N1 * p.ldx;
+  float* sr = p.sdw + (size_t)m * N1 * p.ldx;
+  int tau = N1;
+  for (int n0 = 0; n0 <= p.N && tau == N1; n0 += BS_ROWS) {
+    float s[BS_ROWS];
+#pragma unroll
+    for (int j = 0; j < BS_ROWS; ++j)
+      s[j] = n0 + j <= p.N ? asian_lane_sum_ahead<false>(xr + (size_t)(n0 + j) * p.ldx + 1, b.cols, l) : 0.f;
+#pragma unroll
+    for (int j = 0; j < BS_ROWS; ++j) {
+#pragma unroll
+      for (int o = 1; o < ASIAN_LANES; o <<= 1) s[j] = rn_add(s[j], __shfl_xor(s[j], o));
+    }
+#pragma unroll
+    for (int j = 0; j < BS_ROWS; ++j) {
+      const float stat = b.mean ? asian_mean(s[j], b.cols) : s[j];
+      if (tau == N1 && n0 + j <= p.N && barrier_hit(stat, b.B, b.gsign)) tau = n0 + j;
+    }
+  }
+  if (tau >= p.N) return;
+  for (int c = l; c < (p.ldx >> 2); c += ASIAN_LANES) {
+    const int c0 = 4 * c;
+    if (c0 > p.D) break;                         // past the last state column
+    const bool whole = c0 >= 1 && c0 + 3 <= p.D;   // columns 4c .. 4c + 3 are all state columns
+    if (whole) {
+      const floatx4 xt = *(const floatx4*)(xr + (size_t)tau * p.ldx + c0);
+      for (int n = tau + 1; n <= p.N; ++n) *(floatx4*)(xr + (size_t)n * p.ldx + c0) = xt;
+      for (int n = tau; n < p.N; ++n) *(floatx4*)(sr + (size_t)n * p.ldx + c0) = floatx4{0.f, 0.f, 0.f, 0.f};
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int col = c0 + k;
+        if (col < 1 || col > p.D) continue;
+        const float xt = xr[(size_t)tau * p.ldx + col];
+        for (int n = tau + 1; n <= p.N; ++n) xr[(size_t)n * p.ldx + col] = xt;
+        for (int n = tau; n < p.N; ++n) sr[(size_t)n * p.ldx + col] = 0.f;
+      }
+    }
+  }
+}
+
 // Q3 (D == 1): S_n = sum over paths of sdw[m, n]   (1d_BSPDE_case.py:271-273)
 __global__ void __launch_bounds__(256) q3_sum_kernel(const float* sdw, int ldx, int M, int N, float* S) {
   const int n = blockIdx.x;

@@ -11,6 +11,7 @@
 // increment GEMM when a factor is set), then rollout_asian_avg_kernel.
 // Geometric average (DBSDE_PROB_GEO_ASIAN): the same two launches, the second
 // its geometric instance.
+// Knock-out (DBSDE_PROB_BARRIER): DIAG's launches, then rollout_barrier_stop_kernel.
 #include <hip/hip_runtime.h>
 
 // a prefetched rollout runs on the next chunked step's second stream
@@ -254,6 +255,22 @@ int launch_paths(dbsde_ctx* c, RolloutArgs& ra, hipStream_t s, bool side = false
   } else {
     const int nthr = ra.M * ra.D;
     RUN(c, s, name, 0.0, bytes, fetch_diag_kernel<<<(nthr + 255) / 256, 256, 0, s>>>(ra));
+  }
+  if (c->barrier && ra.out == PATH_ROLLOUT) {
+    // knock-out problems: the rows above are DIAG's, whichever form wrote them; the
+    // stop pass (paths.hpp) follows on the same stream.  It reads the payoff's
+    // columns of every row up to the hit and rewrites the rows behind it.
+    const dbsde_problem& pr = c->cfg.problem;
+    BarrierArgs ba{};
+    ba.B = pr.h_kappa;
+    ba.gsign = pr.g_kind >= DBSDE_G_PUT_SUM ? -1.f : 1.f;
+    ba.cols = c->gcols;
+    ba.mean = pr.g_kind == DBSDE_G_CALL_MEAN || pr.g_kind == DBSDE_G_PUT_MEAN;
+    if (ba.cols < 1 || ba.cols > ra.D || c->asian || c->heston || c->heston2)
+      return fail(c, DBSDE_EINVAL, "internal: barrier stop pass geometry");
+    const long long groups = (long long)ra.M * ASIAN_LANES;
+    RUN(c, s, "barrier_stop", 1.0 * ra.M * (ra.N + 1.0) * ba.cols, 4.0 * ra.M * (ra.N + 1.0) * ba.cols,
+        rollout_barrier_stop_kernel<<<(unsigned)((groups + BS_THREADS - 1) / BS_THREADS), BS_THREADS, 0, s>>>(ra, ba));
   }
   return DBSDE_OK;
 }

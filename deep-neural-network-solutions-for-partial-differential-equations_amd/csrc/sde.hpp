@@ -9,6 +9,8 @@
 // without hipcc, and tests/test_sde_step_cpu.py checks these functions against
 // the oracles on a CPU.
 #pragma once
+#include <stddef.h>
+
 #include "rn.hpp"
 
 namespace dbsde {
@@ -149,6 +151,35 @@ DBSDE_HD float geo_row_sum(const float* S, int k) {
     for (int l = 0; l < ASIAN_LANES; ++l) p[l] = q[l];
   }
   return p[0];
+}
+
+// Knock-out (barrier) problems (DBSDE_PROB_BARRIER): the DIAG process stopped
+// at the first monitored row whose payoff statistic is beyond the barrier B.
+// The statistic is the payoff's own over its `cols` leading state columns, in
+// asian_row_sum's order; every comparison is fp32.  gsign > 0 (the calls):
+// down-and-out, hit when stat <= B; gsign < 0 (the puts): up-and-out, hit when
+// stat >= B.  A NaN statistic never hits.
+DBSDE_HD float barrier_stat(const float* X, int cols, bool mean) {
+  const float s = asian_row_sum(X, cols);
+  return mean ? asian_mean(s, cols) : s;
+}
+DBSDE_HD bool barrier_hit(float stat, float B, float gsign) { return gsign > 0.f ? stat <= B : stat >= B; }
+// One path's rows: X and S point at the first state column of row 0 of the
+// path's xin and sdw rows (row stride ld, rows 0..N, D state columns).  tau is
+// the first row n in 0..N that hits; rows n > tau of X get row tau's state
+// columns, rows n >= tau of S get 0; nothing else is touched (t keeps
+// running).  Returns tau, N + 1 for a path that never hits (it is left as it
+// is).  The device pass (rollout_barrier_stop_kernel, paths.hpp) restates this
+// rule over a 16-lane group.
+DBSDE_HD int barrier_stop(float* X, float* S, int ld, int N, int D, int cols, bool mean, float B, float gsign) {
+  int tau = N + 1;
+  for (int n = 0; n <= N && tau > N; ++n)
+    if (barrier_hit(barrier_stat(X + (size_t)n * ld, cols, mean), B, gsign)) tau = n;
+  for (int n = tau + 1; n <= N; ++n)
+    for (int d = 0; d < D; ++d) X[(size_t)n * ld + d] = X[(size_t)tau * ld + d];
+  for (int n = tau; n <= N; ++n)
+    for (int d = 0; d < D; ++d) S[(size_t)n * ld + d] = 0.f;
+  return tau;
 }
 
 }  // namespace dbsde

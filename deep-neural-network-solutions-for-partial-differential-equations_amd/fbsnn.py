@@ -225,8 +225,8 @@ class FBSNN(ABC):
             why = "no problem_spec()"
         else:
             bad = generic.coefficient_mismatches(self, FBSNN, spec, self.state_dim, self.T, self.Xi, self.device)
-            if bad and (spec.kind != "diag" or spec.average):
-                kind = "running-average" if spec.average else repr(spec.kind)
+            if bad and (spec.kind != "diag" or spec.average or spec.barrier):
+                kind = "running-average" if spec.average else ("knock-out" if spec.barrier else repr(spec.kind))
                 raise NotImplementedError(f"{type(self).__name__} overrides {', '.join(bad)} of a {kind} "
                                           "problem; only DIAG-shaped problems run user coefficient methods")
             if bad:

@@ -23,6 +23,10 @@ methods (generic.py) instead of silently training the parent's problem.
   AmericanPutOption / AmericanBasketPutOption
                         (no reference counterpart)      PutOption / BasketPutOption with early exercise,
                                                         by penalisation: phi -= penalty (g(X) - Y)^+
+  BarrierCallOption / BarrierPutOption, BarrierBasketCallOption / BarrierBasketPutOption
+                        (no reference counterpart)      CallOption / PutOption / BasketCallOption /
+                                                        BasketPutOption knocked out at a barrier
+                                                        (down-and-out calls, up-and-out puts)
   BlackScholesBarenblatt: see deepbsde.py (DeepBSDE.py:326-341 surface)
 """
 from __future__ import annotations
@@ -742,8 +746,118 @@ class AmericanBasketPutOption(_AmericanPut, BasketPutOption):
     penalty=100.0.  No multi-asset arbiter: tree_value needs D = 1."""
 
 
+class _KnockOut:
+    """A knock-out barrier on the parent's option (problem kind
+    DBSDE_PROB_BARRIER, ProblemSpec(barrier=B)): keyword barrier=B > 0.  The
+    calls are down-and-out (B <= strike), the puts up-and-out (B >= strike);
+    the monitored statistic is the payoff's own (the sum of the assets for
+    CallOption / PutOption, their mean for the baskets), checked at the grid
+    times t_0..t_N, no rebate.  Training runs on the stopped paths X_{t ^ tau}
+    (rows behind the knock-out row hold its state, their sigma dW is 0), on
+    which the BSDE loss itself teaches u = 0 beyond the barrier; predict and
+    loss_function return the stopped X.  fetch_minibatch still returns the
+    unstopped Brownian path: the stop pass follows every rollout.
+
+    european() is the twin without the barrier (an upper bound), closed_form
+    the Reiner-Rubinstein price for one asset, mc_value the knocked-out
+    Monte-Carlo value on the training scheme (D <= 128; delta=True raises: bump
+    and reprice on the same draws).  Limits: no knock-in, rebate, reverse or
+    double barrier, no bridge correction between grid times, no barrier on
+    Heston, Asian or American problems; pde_residual is meaningful on the live
+    side only; a subclass overriding a coefficient method with other
+    coefficients is refused (NotImplementedError): the generic rollout does not
+    stop paths.  barrier=0 builds the parent's problem (european() does)."""
+
+    def __init__(self, *args, barrier, **kw):
+        barrier = float(barrier)
+        if not (barrier >= 0.0 and math.isfinite(barrier)):
+            raise ValueError("barrier must be finite and > 0 (0: no barrier)")
+        self.barrier = barrier
+        self._ctor = (args, dict(kw))
+        super().__init__(*args, **kw)
+
+    def problem_spec(self):
+        spec = super().problem_spec()
+        return dataclasses.replace(spec, barrier=self.barrier, q3=False) if self.barrier else spec
+
+    def european(self):
+        """The same option without the barrier: a new object built from this
+        one's constructor arguments with barrier=0, its own (freshly initialised)
+        network and this object's correlation, as _AmericanPut.european builds
+        its twin.  Its value bounds the knock-out value from above, path by path
+        on the same draws.  The caller's numpy and torch (CPU) random streams are
+        left where they were."""
+        args, kw = self._ctor
+        np_state, torch_state = np.random.get_state(), torch.get_rng_state()
+        try:
+            twin = type(self)(*args, barrier=0.0, **kw)
+        finally:
+            np.random.set_state(np_state)
+            torch.set_rng_state(torch_state)
+        twin.correlation_matrix = np.array(self.correlation_matrix, copy=True)
+        twin._L = None if self._L is None else np.array(self._L, copy=True)
+        if twin._L is not None:
+            twin.solver.set_corr(twin._L)
+        return twin
+
+    def closed_form(self, t, X, monitoring="discrete"):
+        """(price [R, 1], delta [R, 1]) of this object's knock-out option at the
+        points (t [R], X [R, 1]): the Reiner-Rubinstein formula
+        (exact("barrier_call" / "barrier_put"), DBSDE_EXACT_BARRIER_*) with the
+        object's r, sigma, strike, cost of carry b = mu_a + phi_r phi_c and
+        barrier.  monitoring="discrete": the barrier is first shifted by the
+        Broadie-Glasserman-Kou factor for this object's grid -- n_mon = N (T - t)
+        / T dates over the remaining time, i.e. a spacing of T / N at every point;
+        "continuous": no shift.  One asset only."""
+        if monitoring not in ("discrete", "continuous"):
+            raise ValueError("monitoring must be 'discrete' or 'continuous'")
+        if self.D != 1:
+            raise ValueError(f"closed_form prices one asset (D = 1); this object has D = {self.D}")
+        if not self.barrier:
+            raise ValueError("closed_form is the knock-out price: this object has no barrier")
+        spec = self.problem_spec()
+        r, sigma, K, b = spec.phi_r, spec.sig_a, float(self.strike), spec.mu_a + spec.phi_r * spec.phi_c
+        X = torch.as_tensor(np.asarray(X) if not isinstance(X, torch.Tensor) else X,
+                            dtype=torch.float32).to(self.device).reshape(-1, 1).contiguous()
+        t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t,
+                            dtype=torch.float32).to(self.device).reshape(-1).contiguous()
+        if t.numel() != X.shape[0]:
+            raise ValueError("t and X must hold the same number of points")
+        kind = "barrier_put" if spec.g.startswith("put") else "barrier_call"
+        price, delta = torch.empty_like(X), torch.empty_like(X)
+        for tv in torch.unique(t).tolist():   # n_mon is one parameter of a call: one call per time
+            sel = t == tv
+            tau = float(self.T) - tv
+            n_mon = self.N * tau / float(self.T) if (monitoring == "discrete" and tau > 0) else 0.0
+            pr, dl = _exact(kind, t[sel], X[sel], self.T, (r, sigma, K, b, self.barrier, n_mon))
+            price[sel], delta[sel] = pr, dl
+        return price, delta
+
+
+class BarrierCallOption(_KnockOut, CallOption):
+    """CallOption (payoff max(sum X - K, 0), phi = r (Y - X.Z)) knocked out when
+    sum X <= barrier at a grid time; keyword barrier= (<= strike)."""
+
+
+class BarrierPutOption(_KnockOut, PutOption):
+    """PutOption (payoff max(K - sum X, 0)) knocked out when sum X >= barrier at a
+    grid time; keyword barrier= (>= strike)."""
+
+
+class BarrierBasketCallOption(_KnockOut, BasketCallOption):
+    """BasketCallOption (payoff max(mean X - K, 0), correlated increments, its
+    schedule and train surface) knocked out when mean X <= barrier at a grid time;
+    keyword barrier= (<= strike)."""
+
+
+class BarrierBasketPutOption(_KnockOut, BasketPutOption):
+    """BasketPutOption (payoff max(K - mean X, 0)) knocked out when mean X >=
+    barrier at a grid time; keyword barrier= (>= strike)."""
+
+
 __all__ = ["CallOption", "PutOption", "CallOption1D", "BasketCallOption", "BasketPutOption", "BSPDETestCase", "HamiltonJacobiBellman",
            "HestonFBSNN", "HestonTwoFactorFBSNN", "AsianCallOption", "AsianPutOption", "AsianBasketCallOption",
            "AsianBasketPutOption", "GeometricAsianCallOption", "GeometricAsianPutOption",
            "GeometricAsianBasketCallOption", "GeometricAsianBasketPutOption", "AmericanPutOption",
-           "AmericanBasketPutOption"]
+           "AmericanBasketPutOption", "BarrierCallOption", "BarrierPutOption", "BarrierBasketCallOption",
+           "BarrierBasketPutOption"]

@@ -36,7 +36,13 @@ class ProblemSpec:
     exp((1/T) int mean_i log S_i dt), G_0 = 1, sig_b = 0; the payoff is on G.
     penalty (kind "diag" without an average and without u_clamp only): lambda
     >= 0 of the penalised American problem, phi -= penalty max(g(X) - Y, 0)
-    with g on the row's own X (dbsde_problem.pen); 0 is the European problem."""
+    with g on the row's own X (dbsde_problem.pen); 0 is the European problem.
+    barrier (kind "diag" without an average, a penalty, q3 or u_clamp only): the
+    level B > 0 of a knock-out barrier monitored at the grid times
+    (DBSDE_PROB_BARRIER; sent in the h_kappa slot): g "call_sum" / "call_mean"
+    knock down (B <= strike), "put_sum" / "put_mean" knock up (B >= strike), on
+    the payoff's own statistic; training runs on the stopped paths.  0 is the
+    problem without a barrier."""
 
     mu_a: float = 0.0
     sig_a: float = 0.0
@@ -55,6 +61,7 @@ class ProblemSpec:
     theta: float = 0.0
     sigma: float = 0.0
     rho: float = 0.0
+    barrier: float = 0.0
     penalty: float = 0.0
     average: bool = False
 
@@ -86,9 +93,18 @@ class ProblemSpec:
                                  "average: Heston and Asian states are not supported")
             if self.u_clamp:
                 raise ValueError("a non-zero penalty cannot be combined with u_clamp")
+        kappa = self.kappa
+        if float(self.barrier) != 0.0:
+            if self.kind != "diag" or average:
+                raise ValueError("a barrier needs kind 'diag' without an average: barriers on Heston or Asian states "
+                                 "are not supported")
+            if self.kappa or self.theta or self.sigma or self.rho:
+                raise ValueError("a barrier problem takes no Heston coefficients (kappa, theta, sigma, rho): the "
+                                 "barrier level travels in the h_kappa slot")
+            kind, kappa = _lib.PROB_BARRIER, float(self.barrier)   # the library checks B, g, strike, pen, q3, u_clamp
         return _lib.Problem(kind, self.mu_a, self.sig_a, self.sig_b, self.phi_r,
                             self.phi_c, self.phi_zz, _lib.G_KINDS[self.g], self.strike, int(self.q3),
-                            int(self.g_cols), self.g_alpha, int(self.u_clamp), self.kappa, self.theta,
+                            int(self.g_cols), self.g_alpha, int(self.u_clamp), kappa, self.theta,
                             self.sigma, self.rho, pen)
 
 
@@ -465,7 +481,14 @@ def exact(kind, t, X, T, params=(), sigma=None, K=None, *, b=None, n_tree=None, 
     >= 0 the value of the penalised problem a ProblemSpec(penalty=...) trains
     on (0: the European tree).  A point whose risk-neutral probability
     (e^{b dt} - d) / (u - d) leaves [0, 1] (a coarse tree, |b| sqrt(dt) > sigma)
-    has no tree value: its price and delta are NaN."""
+    has no tree value: its price and delta are NaN.
+
+    "barrier_call" / "barrier_put": the down-and-out call (B <= K) and the
+    up-and-out put (B >= K) without rebate on every coordinate of X [R, D]
+    (Reiner-Rubinstein), params = (r, sigma, K, b, B, n_mon): b the cost of carry,
+    n_mon > 0 the number of monitoring dates over the remaining time (the
+    Broadie-Glasserman-Kou shift of B), 0 continuous monitoring; price and delta
+    [R, D], both 0 beyond the barrier."""
     lib = _lib.load()
     if kind not in _lib.EXACT_KINDS:
         raise ValueError(f"unknown exact solution {kind!r}")
@@ -485,6 +508,9 @@ def exact(kind, t, X, T, params=(), sigma=None, K=None, *, b=None, n_tree=None, 
         params = (r_, sigma, K, r_ if b is None else b, nt, float(math.inf if penalty is None else penalty))
     elif any(v is not None for v in (sigma, K, b, n_tree, penalty)):
         raise ValueError(f"sigma, K, b, n_tree and penalty are arguments of 'american_put', not of {kind!r}")
+    bar = kind in ("barrier_call", "barrier_put")
+    if bar and (not hasattr(params, "__len__") or len(params) != 6):
+        raise ValueError(f"{kind!r} takes params = (r, sigma, K, b, B, n_mon)")
     X = X.reshape(X.shape[0], -1).contiguous().float()
     t = t.reshape(-1).contiguous().float()
     R, D = X.shape
@@ -494,12 +520,12 @@ def exact(kind, t, X, T, params=(), sigma=None, K=None, *, b=None, n_tree=None, 
     geo = kind in ("geo_asian", "geo_asian_put")
     if geo and D < 2:
         raise ValueError(f"{kind!r} takes X [R, 1 + k] = [G, S_1..S_k]")
-    ncol = D if kind in ("bs_call", "bs_put", "american_put") else 1
+    ncol = D if kind in ("bs_call", "bs_put", "american_put") or bar else 1
     price = torch.empty((R, ncol), device=X.device)
     delta = None if kind == "bsb" else torch.empty((R, D if geo else ncol), device=X.device)
     import numpy as np
     p = np.zeros(6, dtype=np.float64)
-    if len(params) > (6 if heston or geo or tree else 3):
+    if len(params) > (6 if heston or geo or tree or bar else 3):
         raise ValueError(f"too many parameters for {kind!r}")
     if heston and len(params) != 6:
         raise ValueError(f"{kind!r} takes params = (r, K, kappa, theta, sigma, rho)")
@@ -542,12 +568,18 @@ def mc_value(spec, t, X, T, n_steps, mc=2 ** 16, seed=0, offset=0, L=None, delta
     and its delta is [dA, dS_1..dS_k] (average="geometric": X = [G, S_1..S_k],
     delta [dG, dS_1..dS_k]; its continuous-time value is exact("geo_asian")).  Returns
     (value [P, 1], stderr [P, 1], delta [P, D] or None); delta is the pathwise
-    estimator (diag only)."""
+    estimator (diag only).  A barrier spec (barrier != 0; D <= 128, L [D, D])
+    gives the knocked-out value exp(-phi_r tau) E[g(X_T) alive] on the same
+    draws; delta=True raises: the pathwise estimator is biased across the
+    knock-out indicator, bump and reprice on the same draws instead."""
     if spec.phi_zz != 0:
         raise ValueError("mc_value needs a linear problem (phi_zz == 0); the HJB comparator is hjb_mc")
     if spec.penalty != 0:
         raise ValueError("mc_value needs a linear problem (penalty == 0); the arbiter of the penalised American put "
                          "is exact('american_put') (DBSDE_EXACT_AMERICAN_PUT)")
+    if float(getattr(spec, "barrier", 0.0)) != 0.0 and delta:
+        raise ValueError("mc_value has no pathwise delta for a barrier problem (the estimator is biased across the "
+                         "knock-out indicator): bump and reprice on the same draws (same seed and offset)")
     if L is not None:   # the checks that need no device
         import numpy as np
         L = np.ascontiguousarray(np.asarray(L.cpu() if isinstance(L, torch.Tensor) else L, dtype=np.float32))

@@ -97,6 +97,13 @@ extern "C" {
                               /* geometric-average Asian option on k GBM assets: state
                                  [G, S_1..S_k], G = exp((1/T) int mean_i log S_i dt) the
                                  running geometric average (nb = D - 1)                */
+/* kind 11 (9, 10 and 12 are unknown kinds), an expression for the same reason;
+   tests/test_abi_barrier.py holds the compiled value to 11 */
+#define DBSDE_PROB_BARRIER (DBSDE_PROB_GEO_ASIAN + 3)
+                              /* knock-out (barrier) option on the DIAG process, monitored at
+                                 the grid times: down-and-out for the call payoffs, up-and-out
+                                 for the puts; state and Brownian dimension DIAG's (nb = D),
+                                 h_kappa holds the barrier level B                      */
 
 /*
  * Problem coefficients (one FBSNN subclass = one filled struct):
@@ -164,6 +171,30 @@ extern "C" {
  *       u(T, .) = g(G),
  *     g_cols = 1.  dbsde_pde_residual takes ASIAN's directions (G component 0) and this
  *     drift (logf of the S columns); dbsde_mc_value simulates the same process (below).
+ *   kind BARRIER, the same struct: DIAG's state, coefficients, Brownian dimension nb = D and
+ *     factor (dbsde_set_corr), with a knock-out barrier monitored at the grid times t_0..t_N
+ *     and no rebate.  kind BARRIER: h_kappa is the barrier level B (the Heston members are
+ *     unused by every non-Heston kind; h_theta, h_sigma and h_rho must be 0).  The monitored
+ *     statistic is the payoff's own over its g_cols columns, every comparison in fp32:
+ *       p_l, butterfly                     ASIAN's row-sum order over columns 1..g_cols
+ *       stat = sum                         (CALL_SUM / PUT_SUM)
+ *       stat = sum / (float)g_cols         (CALL_MEAN / PUT_MEAN)
+ *       call: knocked at the first row n with stat_n <= B (down-and-out; row 0 counts)
+ *       put:  knocked at the first row n with stat_n >= B (up-and-out)
+ *     Only the regular barriers: B <= strike for a call, B >= strike for a put, so g is 0
+ *     with gradient 0 on a knocked state.  Training runs on the stopped process X_{t ^ tau}:
+ *     rows n <= tau are the unstopped path's, rows n > tau hold X_tau, sdw rows n >= tau are
+ *     0, t keeps running (the stop pass follows every rollout form; dbsde_brownian still
+ *     returns the unstopped Brownian path).  On the frozen rows the BSDE residual is
+ *     u(t_{n+1}, x) - u(t_n, x) - phi dt with terminal value g(x) = 0: u = 0, Du = 0, the
+ *     Dirichlet condition (a non-zero rebate would not be consistent with a
+ *     discounting driver on the frozen rows).  DBSDE_EINVAL from dbsde_create and
+ *     dbsde_mc_value, before any HIP call and naming the field: h_kappa <= 0, NaN or
+ *     infinite; a call with h_kappa > strike or a put with h_kappa < strike; g_kind SUMSQ,
+ *     LOG, SMOOTH_CALL or SMOOTH_PUT; pen != 0, q3, u_clamp; h_theta, h_sigma or h_rho != 0.
+ *     dbsde_pde_residual takes DIAG's terms: the generators of the stopped and the unstopped
+ *     process agree on the live side of the barrier, and the residual means nothing beyond
+ *     it.  dbsde_mc_value simulates the knocked-out payoff (below).
  *   phi      =phi_r * (Y - phi_c * X.Z) + phi_zz * |Z|^2
  *   g        = g_kind over the first g_cols state columns (0 = all), strike,
  *              g_alpha (DBSDE_G_SMOOTH_CALL / _PUT); the terminal |Z - grad g|^2 term
@@ -257,7 +288,7 @@ int dbsde_param_used_mask(const dbsde_ctx* ctx, unsigned char* mask, long long n
  * create time (DBSDE_X3=0 / DBSDE_TNW_X3=0 select the fp32 forms). */
 int dbsde_matrix_form(const dbsde_ctx* ctx);
 
-/* Brownian dimension nb of a batch's W [M, N+1, nb]: D (DIAG, HESTON2), D/2 for HESTON,
+/* Brownian dimension nb of a batch's W [M, N+1, nb]: D (DIAG, HESTON2, BARRIER), D/2 for HESTON,
    D - 1 for ASIAN and GEO_ASIAN */
 int dbsde_brownian_dim(const dbsde_ctx* ctx);
 
@@ -579,8 +610,29 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
  *                            on the point's tau, which the host does not read: a point
  *                            whose p is not in [0, 1] (a coarse tree, |b| sqrt(Delta) >
  *                            sigma) has no tree value and gets NaN in price and delta.
+ *   DBSDE_EXACT_BARRIER_CALL (15), DBSDE_EXACT_BARRIER_PUT (16)
+ *                            the down-and-out call / up-and-out put without rebate on one
+ *                            GBM asset (Reiner and Rubinstein 1991), B <= K / B >= K: every
+ *                            coordinate of x [R, D] is priced on its own, ncol = D, params =
+ *                            {r, sigma, K, b, B, n_mon}, b the cost of carry.  With
+ *                            lambda = (b - sigma^2 / 2) / sigma^2, s = sigma sqrt(tau),
+ *                              x1 = ln(S / K) / s + (1 + lambda) s
+ *                              y1 = ln(B^2 / (S K)) / s + (1 + lambda) s
+ *                              A = f S e^{(b - r) tau} N(f x1) - f K e^{-r tau} N(f x1 - f s)
+ *                              C = f S e^{(b - r) tau} (B / S)^{2 (lambda + 1)} N(f y1)
+ *                                  - f K e^{-r tau} (B / S)^{2 lambda} N(f y1 - f s)
+ *                            the price is A - C, f = +1 (call), -1 (put); delta is its
+ *                            analytic derivative in S.  n_mon > 0: the barrier is monitored
+ *                            at n_mon equally spaced dates over tau and B is first moved
+ *                            away from S by exp(-+0.5826 sigma sqrt(tau / n_mon)) (Broadie,
+ *                            Glasserman and Kou 1997: down for the call, up for the put);
+ *                            n_mon = 0: continuous monitoring.  Price and delta are 0 for S
+ *                            on the knocked side of the (shifted) barrier; tau <= 0 returns
+ *                            the payoff and its kink delta, 0 when S is beyond the unshifted
+ *                            B.  DBSDE_EINVAL for sigma, K or B <= 0, a call with B > K, a
+ *                            put with B < K, n_mon < 0 or NaN, non-finite r or b.
  * t [R], x [R, D] device fp32; price [R * ncol] and delta (nullable),
- * ncol = D for BS_CALL / BS_PUT / AMERICAN_PUT, 1 otherwise (GEO_ASIAN: price [R], delta [R, D]).  At t >= T the payoff and its
+ * ncol = D for BS_CALL / BS_PUT / AMERICAN_PUT / BARRIER_CALL / BARRIER_PUT, 1 otherwise (GEO_ASIAN: price [R], delta [R, D]).  At t >= T the payoff and its
  * 0 / 1/2 / 1 (put: 0 / -1/2 / -1) delta are returned, as the references do.
  * Computed in fp64.  DBSDE_EINVAL before any HIP call: an unknown kind; NULL t /
  * x / params / price; R or D < 1; a Heston kind with D != 2; a GEO_ASIAN kind with D < 2; t, x, price or
@@ -599,6 +651,8 @@ int dbsde_lbfgs_direction(dbsde_ctx* ctx, const float* g, const float* S, const 
 #define DBSDE_EXACT_GEO_ASIAN 10
 #define DBSDE_EXACT_GEO_ASIAN_PUT 11
 #define DBSDE_EXACT_AMERICAN_PUT 14
+#define DBSDE_EXACT_BARRIER_CALL 15
+#define DBSDE_EXACT_BARRIER_PUT 16
 int dbsde_exact(int kind, const float* t, const float* x, long long R, int D, float T, const double* params,
                 float* price, float* delta, void* hip_stream);
 
@@ -653,6 +707,18 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * / S_{d,n}) dt_n)) / (k T).  L [k, k], k <= 128.  tau_p <= 0 returns g(G_p), 0 and
  * (g', 0, .., 0).  Its exact value in continuous time is DBSDE_EXACT_GEO_ASIAN; the
  * scheme differs from it by O(dt).
+ * BARRIER (x [P, D], DIAG's state): the value is exp(-phi_r tau_p) mean_k g(X_N) alive_k,
+ * alive_k = no row n = 0..n_steps of sample k's path was knocked (the rule of the problem
+ * kind above: the statistic in fp32 in the rollout's row-sum order, so a restatement
+ * reproduces every flag); the standard error is that of the same summand.  A 16-lane
+ * group runs one sample of one point, lane l the assets l, l + 16, ..; g(X_N) takes the
+ * fp64 sum of the lanes' ascending fp64 partial sums met in the same butterfly.  Drift
+ * mu_eff, DIAG's step and draws, common to all points.  nb = D <= 128 with or without L
+ * (above: DBSDE_EINVAL).  With L the unscaled L z come from HESTON_CORR's increment
+ * workspace (the same bound and grouping).  delta != NULL is DBSDE_EINVAL: the pathwise
+ * estimator is biased across the knock-out indicator; bump and reprice on the same
+ * draws instead.  tau_p <= 0 returns g(x_p) and 0 for a live point, 0 and 0 for a
+ * knocked one.
  *
  *   L       device [nb, nb] row-major lower Cholesky factor (the lower triangle is
  *           read), NULL = independent increments; DIAG: nb = D <= 128;
@@ -688,7 +754,8 @@ int dbsde_hjb_mc(const float* t, const float* x, int P, int D, float T, long lon
  * k = D / 2 > 511; an unknown kind or g_kind; phi_zz != 0; pen != 0 (not linear:
  * the arbiter of a penalised problem is DBSDE_EXACT_AMERICAN_PUT); ASIAN with D < 2,
  * phi_c != 0, g_cols != 1, g_kind SUMSQ or LOG, or L with D - 1 > 128; GEO_ASIAN with any
- * of those or sig_b != 0.  Needs no context;
+ * of those or sig_b != 0; BARRIER with any refusal of the problem kind above, D > 128 or
+ * delta != NULL.  Needs no context;
  * the work is enqueued on hip_stream.
  */
 int dbsde_mc_value(const dbsde_problem* prob, int D, float T, const float* L, const float* t, const float* x, int P,
